@@ -9,10 +9,17 @@ field, hash grid L=16 T=2^19, 64 samples/ray, no proposal nets; rank r renders c
 Cameras.generate_rays -> Model.get_outputs_for_camera_ray_bundle, followed (N>1) by the RCCL all-gather of the finished
 [H,W,4] tiles (started asynchronously: it overlaps the next step's render; all K gathers complete inside the timed region).
 Weak scaling: per-GPU work is fixed.  Inputs (weights, camera) are resident in HBM before the timed region.
+A plain run sets up, warms up, times the K steps and prints the line; everything else it can measure or check (the one-stream
+per-launch leg, roofs, traffic, the other precision, other configurations, the CPU baseline, the N > 1 preflight and post-run
+checks) runs only with --full.  --dump-outputs DIR writes the arrays the last timed step returned as DIR/<name>.npy (float32 /
+float64; a fixed seeded sample of each array when they would exceed 64 MB in all): the inputs are fixed, so two builds can be
+compared output for output.
 Prints ONE JSON line (see DESIGN.md "Measurement"):
   value            whole-job ray-samples/s over the K timed steps (wall clock between barriers + device syncs, max over ranks)
                    Consecutive steps go to --frames-in-flight (default 2) alternating HIP streams: frames are independent, so the head of
                    one fills the wave slots the tail of the previous leaves idle (800x800 = 3.26 rounds of waves; signerf_amd.sheet.FrameStreams)
+  ms_per_step      wall-clock milliseconds of one timed step
+  --full adds:
   kernel_ms        HIP-event time of a render call alone on the chip (one-stream leg after the timed region): mean / median / min / max / p05 / p95
   roofline         the hardware issue roof that binds the dominant kernel (K1 sn_render_main_kernel), as a fraction < 1: instruction
                    counts per wave-step come from the disassembly of the loaded library (tools/kernel_counts.py), the clock from
@@ -170,6 +177,37 @@ def _json_line_of(cmd, timeout_s, env=None, cwd=None):
         return None, "rc %d: %s" % (r.returncode, (r.stderr or r.stdout)[-300:])
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6   # --dump-outputs: at most 64 MB of .npy files in all
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Writes every tensor of `arrays` ({name: tensor}) as out_dir/<name>.npy: floating types as float32 (float64 stays float64), other
+    types as float64.  When the files would exceed `budget` bytes, each array is replaced by the same share of its elements, flattened, at
+    indices drawn by a generator seeded with `seed` (sorted): the sample depends only on the array's size, so two builds compare element
+    for element.  Returns {name: {"shape", "dtype", "sampled"}}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        a = a.double() if a.dtype == torch.float64 or not a.is_floating_point() else a.float()
+        host[name] = a.contiguous().numpy()
+    header = 128                                                   # a .npy header per file
+    total = sum(a.nbytes + header for a in host.values())
+    share = 1.0 if total <= budget else (budget - header * len(host)) / sum(a.nbytes for a in host.values())
+    info = {}
+    for name, a in host.items():
+        full_shape, sampled = list(a.shape), share < 1.0
+        if sampled:
+            k = int(a.size * share)
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = {"shape": full_shape, "dtype": str(a.dtype), "sampled": sampled}
+    return info
+
+
 def other_configs(precision):
     """BASELINE.json configs[3] and configs[4] in the driver's line: untimed legs AFTER the headline's timed region, each in
     a child process of this interpreter so that the headline's handle, streams and allocator state are not disturbed.
@@ -178,7 +216,7 @@ def other_configs(precision):
       + (r04) `tools/tcnn_modes_bench.py`: the headline frame on a tiny-cuda-nn grid, fp32-grade default vs the opt-in single-fp16 mode"""
     out = []
     me = os.path.abspath(__file__)
-    base = [sys.executable, me, "--workload", "nerfacto1080", "--steps", "12", "--warmup", "3", "--precision", precision, "--no-cpu-baseline",
+    base = [sys.executable, me, "--full", "--workload", "nerfacto1080", "--steps", "12", "--warmup", "3", "--precision", precision, "--no-cpu-baseline",
             "--no-alt-precision", "--no-others", "--no-traffic"]
     d, err = _json_line_of(base, 200)
     if d is None:
@@ -229,7 +267,7 @@ def big_table_leg(precision, log2_t=21):
     PMC passes (TCC_EA0_RDREQ_*, WRITE_SIZE, TCC_HIT / TCC_MISS) of the same command."""
     me = os.path.abspath(__file__)
     extra = ["--log2-hashmap-size", str(log2_t)]
-    d, err = _json_line_of([sys.executable, me, "--steps", "12", "--warmup", "3", "--precision", precision, "--no-cpu-baseline", "--no-alt-precision",
+    d, err = _json_line_of([sys.executable, me, "--full", "--steps", "12", "--warmup", "3", "--precision", precision, "--no-cpu-baseline", "--no-alt-precision",
                             "--no-others", "--no-traffic", *extra], 200)
     name = f"BASELINE configs[1] frame with T = 2^{log2_t} rows per level ({(16 << log2_t) * 8 >> 20} MiB table)"
     if d is None:
@@ -270,7 +308,7 @@ def inrun_traffic(precision, kernel_pattern="sn_render_main_kernel", extra_args=
     tmp = tempfile.mkdtemp(prefix="sn_traffic_")
     env = dict(os.environ, TMPDIR="/tmp")
     me = os.path.abspath(__file__)
-    child = [sys.executable, me, "--steps", "3", "--warmup", "1", "--frames-in-flight", "1", "--precision", precision, "--no-cpu-baseline",
+    child = [sys.executable, me, "--full", "--steps", "3", "--warmup", "1", "--frames-in-flight", "1", "--precision", precision, "--no-cpu-baseline",
              "--no-alt-precision", "--no-others", "--no-traffic", *extra_args]
     acc = {}
     passes = [("rd", ["TCC_EA0_RDREQ_32B_sum", "TCC_EA0_RDREQ_64B_sum", "TCC_EA0_RDREQ_128B_sum"]), ("wr", ["WRITE_SIZE"])]
@@ -511,6 +549,13 @@ def main():
                     help="consecutive steps are issued on this many alternating HIP streams (signerf_amd.sheet.FrameStreams: frames of "
                          "different cameras are independent, the head of one fills the wave slots the tail of the previous leaves idle); "
                          "1 = one stream, every launch waits for the previous one to drain")
+    ap.add_argument("--full", action="store_true",
+                    help="after the line's own measurement, also run everything else the benchmark measures or checks: the one-stream per-launch "
+                         "leg (kernel_ms), issue roofs and sustained clock, traffic, the other precision, the other configurations, the CPU "
+                         "baseline, and for N > 1 the preflight, per-rank checks and gather diagnostics (the --no-* options below trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB in all "
+                         "(a fixed seeded sample of each array beyond that)")
     ap.add_argument("--no-alt-precision", action="store_true", help="skip the extra (untimed-region) run of the other precision")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-others", action="store_true", help="skip the untimed legs of BASELINE.json configs[3] and configs[4] (`others` in the line)")
@@ -620,8 +665,11 @@ def main():
 
     frames = sheet.FrameStreams(dev, max(1, args.frames_in_flight))
     issued = [0]
+    last_out = [None]  # --dump-outputs: (timed step number, 0 in warm-up; the outputs dict of that step's latest render -- what a caller receives)
+    n_timed = [0]      # timed steps issued so far
 
     def step(timed: bool):
+        n_timed[0] += timed
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
         handle = None
@@ -631,6 +679,8 @@ def main():
             out = model.get_outputs_for_camera_ray_bundle(bundle)
             e1.record()
             tile = frames.keep(torch.cat([out["rgb"], out["depth"]], dim=-1)[None])
+            if args.dump_outputs:
+                last_out[0] = (n_timed[0], dict(dict.items(out)))   # the entries the call computed (lazy normals, and the workspace they hold, let go)
             if world > 1:
                 # depth-1 pipeline: this frame's all-gather (RCCL's own stream, ordered behind this step's stream) overlaps the next
                 # frames' renders; every gather is waited for inside the timed region (drain() below)
@@ -652,6 +702,7 @@ def main():
     def sheet_step(timed: bool):
         """--scaling strong: one whole sheet.  This rank renders its cameras (i mod N == rank) on the alternating streams, the caller's
         stream joins them, ONE gather moves the tiles; the gather of sheet k overlaps the renders of sheet k + 1 (depth-1 pipeline)."""
+        n_timed[0] += timed
         tiles = []
         for i in mine:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -661,6 +712,8 @@ def main():
                 out = model.get_outputs_for_camera_ray_bundle(bundle)
                 e1.record()
                 tiles.append(frames.keep(torch.cat([out["rgb"], out["depth"]], dim=-1)))
+                if args.dump_outputs:
+                    last_out[0] = (n_timed[0], dict(dict.items(out)))
             issued[0] += 1
             if timed:
                 render_ms.append((e0, e1))
@@ -706,7 +759,10 @@ def main():
 
     model._ensure_engine()  # library load, weight upload and de-hashed copies are set-up, not a step (matters only for --warmup 0)
     torch.cuda.synchronize()
-    pre = preflight(world, rank, dev, args.backend, shared_gpu) if world > 1 else {"preflight": "n/a (one rank)", "device_name": device_identity(dev)["name"]}
+    if world > 1 and args.full:
+        pre = preflight(world, rank, dev, args.backend, shared_gpu)
+    else:
+        pre = {"preflight": "n/a (one rank)" if world == 1 else "not run (--full runs it)", "device_name": device_identity(dev)["name"]}
     step_fn = sheet_step if strong else step
     if args.warmup < args.frames_in_flight:
         # every render stream allocates its output / workspace blocks on first use (hipMalloc): one priming frame per stream is set-up
@@ -736,10 +792,19 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned: the render call's outputs (the entries it computed; lazy normals are not asked for) and, when a
+        # step hands back more than one camera, the step's tiles
+        from_step, arrays = last_out[0]
+        if tiles is not None and (world > 1 or strong):
+            arrays["tiles"] = tiles
+        dumped = {"dir": args.dump_outputs, "timed_step": from_step, "arrays": dump_outputs(args.dump_outputs, arrays)}
+        last_out[0] = arrays = None
     latency = sorted(a.elapsed_time(b) for a, b in render_ms)  # with several frames in flight: the span of a call that shared the chip
     # Per-launch time of the render call with nothing else on the chip: an untimed-region leg on ONE stream (what rocprofv3 reports for
     # `bench.py --frames-in-flight 1`, profiles/); the roofline fractions below are per launch and use this.
-    if args.frames_in_flight > 1:
+    if args.full and args.frames_in_flight > 1:
         serial = []
         for i in range(min(args.steps, 100) + 6):  # (the first calls on this stream allocate their buffers afresh)
             bundle = cam.generate_rays(camera_indices=0, aabb_box=model.render_aabb)
@@ -828,7 +893,7 @@ def main():
         run_with_watchdog(legs, args.diagnostics_timeout if rank == 0 else args.diagnostics_timeout + 240.0, bail)   # (rank 0 builds its line first)
         return by, err[0]
 
-    if world > 1 and rank != 0:
+    if world > 1 and rank != 0 and args.full:
         run_post_checks()
         gather_diagnostics()
     if rank == 0:
@@ -876,15 +941,18 @@ def main():
             "gather_ms": None,   # (world > 1: filled in below, after the line's own measurements)
             "timed_region_s": elapsed,
             "frames_in_flight": max(1, args.frames_in_flight),
-            # for comparison with one-launch-at-a-time figures (r01's lines, rocprofv3): samples of one frame over the per-launch time
-            "one_stream_ray_samples_per_s_per_gpu": W * H * S / (k_med * 1e-3),
-            # SURVEY 8(d) metric (1) as written: samples of one frame over the HIP-event time of ONE get_outputs_for_camera_ray_bundle call
-            # with nothing else in flight (median); `value` above is the job's pipelined rate (frames_in_flight)
-            "value_one_launch_at_a_time": (W * H * S / (k_med * 1e-3)) if world == 1 else None,
-            "kernel_ms": {"mean": kernel_ms, "median": k_med, "min": per_step[0], "max": per_step[-1], "p05": pct(0.05), "p95": pct(0.95), "n": n_steps,
-                          "what": "HIP-event time of a render call on its launch stream with nothing else in flight (K1 + two memsets + the clip "
-                                  "kernel; + K2 with proposal nets)" + ("; measured in a one-stream leg after the timed region -- the timed steps "
-                                  "overlap the tail of one frame with the head of the next, see frame_latency_ms" if args.frames_in_flight > 1 else "")},
+            # --full: the one-stream leg after the timed region (kernel_ms) and what is derived from it
+            **({
+                # for comparison with one-launch-at-a-time figures (r01's lines, rocprofv3): samples of one frame over the per-launch time
+                "one_stream_ray_samples_per_s_per_gpu": W * H * S / (k_med * 1e-3),
+                # SURVEY 8(d) metric (1) as written: samples of one frame over the HIP-event time of ONE get_outputs_for_camera_ray_bundle call
+                # with nothing else in flight (median); `value` above is the job's pipelined rate (frames_in_flight)
+                "value_one_launch_at_a_time": (W * H * S / (k_med * 1e-3)) if world == 1 else None,
+                "kernel_ms": {"mean": kernel_ms, "median": k_med, "min": per_step[0], "max": per_step[-1], "p05": pct(0.05), "p95": pct(0.95), "n": n_steps,
+                              "what": "HIP-event time of a render call on its launch stream with nothing else in flight (K1 + two memsets + the clip "
+                                      "kernel; + K2 with proposal nets)" + ("; measured in a one-stream leg after the timed region -- the timed steps "
+                                      "overlap the tail of one frame with the head of the next, see frame_latency_ms" if args.frames_in_flight > 1 else "")},
+            } if args.full else {}),
             "frame_latency_ms": {"median": statistics.median(latency), "p05": latency[int(0.05 * len(latency))], "p95": latency[int(0.95 * len(latency))],
                                  "what": "HIP-event span of each TIMED render call on its own stream (with %d frames in flight a call shares the "
                                          "chip with its neighbours: the span grows, the frame period ms_per_step shrinks)" % max(1, args.frames_in_flight)},
@@ -892,7 +960,16 @@ def main():
             # SURVEY §8(d) metric (3): every field evaluation of a ray (proposal nets + main field)
             "field_evaluations_per_sec": cams_per_step * W * H * (S + (sum(cfg.num_proposal_samples_per_ray[:cfg.num_proposal_iterations])
                                                                if args.workload != "sheet64" else 0)) * args.steps / elapsed,
+            "full": args.full,
         }
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
+        if not args.full:
+            print(json.dumps(line), flush=True)
+            if world > 1:
+                dist.barrier()
+                dist.destroy_process_group()
+            return
         achieved_gbps = (W * H * bytes_per_ray) / (k_med * 1e-3) / 1e9
         traffic, traffic_commit = measured_traffic(args.precision) if args.workload == "sheet64" else (None, None)
         # HBM-side bytes per launch: measured IN THIS RUN by two rocprofv3 --pmc child passes (inrun_traffic; N = 1, the headline workload);

@@ -19,7 +19,7 @@ INV=$(awk '{for(i=1;i<=8;i++)s[i]+=$i; n++} END{for(i=1;i<=8;i++)printf "%d%s", 
 echo "per-XCD clocks under load (MHz, mean of 8 samples): $W"
 one() {  # label, weights-or-empty
   if [ -n "$2" ]; then export SN_XCD_WEIGHTS=$2; else unset SN_XCD_WEIGHTS; fi
-  python bench.py --steps 200 --warmup 10 --no-others --no-traffic --no-cpu-baseline --no-alt-precision 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1', 'frame period (2 in flight) %.4f ms' % d['ms_per_step'], '| per launch median %.4f' % d['kernel_ms']['median'], '| clock %.3f' % d['roofline']['sustained_clock_ghz'])"
+  python bench.py --full --steps 200 --warmup 10 --no-others --no-traffic --no-cpu-baseline --no-alt-precision 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$1', 'frame period (2 in flight) %.4f ms' % d['ms_per_step'], '| per launch median %.4f' % d['kernel_ms']['median'], '| clock %.3f' % d['roofline']['sustained_clock_ghz'])"
 }
 for rep in 1 2 3; do
   one "equal   " ""

@@ -94,7 +94,7 @@ def gather_tiles_async(local_tiles: Tensor, n_items: int, group=None, dst: Optio
                      and receives per rank, one per link); with ``dst`` only the sends to / receives at the root
       "all_to_all"   ``all_to_all_single`` of the tile replicated per destination: the same direct pushes as one RCCL call
                      (costs a world-fold staging copy of the tile)
-    The result is identical; `bench.py --gpus N` reports the exposed time of each so that the first multi-GPU run compares them."""
+    The result is identical; `bench.py --full --gpus N` reports the exposed time of each so that the first multi-GPU run compares them."""
     if strategy not in GATHER_STRATEGIES:
         raise ValueError(f"gather strategy {strategy!r}: one of {GATHER_STRATEGIES} expected")
     if not (dist.is_available() and dist.is_initialized()):

@@ -84,3 +84,29 @@ def test_issue_port_pricing_by_opcode_class():
     cyc, by = bench.issue_port_cycles({"v_fmac_f32": 10, "v_cvt_pkrtz_f16_f32": 5, "v_exp_f32": 2, "v_cndmask_b32": 1, "v_mfma_f32_32x32x16_f16": 3, "v_never_heard_of": 1})
     assert cyc == 10 * 2 + 5 * 4 + 2 * 8 + 20 + 3 * 4 + 4
     assert by == {"2-cycle": 10, "4-cycle": 6, "8-cycle": 2, "20-cycle": 1, "mfma issue (4)": 3}
+
+
+def test_dump_outputs_writes_every_array_and_samples_beyond_the_budget(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float32 / float64; beyond the byte budget a fixed seeded sample of each array, the
+    same from run to run, within the budget."""
+    import numpy as np
+    import torch
+
+    arrays = {"rgb": torch.arange(3000, dtype=torch.float32).reshape(10, 100, 3), "hit": torch.ones(7, dtype=torch.bool),
+              "t": torch.linspace(0, 1, 50, dtype=torch.float64)}
+    info = bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert sorted(p.name for p in (tmp_path / "all").iterdir()) == ["hit.npy", "rgb.npy", "t.npy"]
+    rgb, hit, t = (np.load(tmp_path / "all" / f"{k}.npy") for k in ("rgb", "hit", "t"))
+    assert rgb.dtype == np.float32 and np.array_equal(rgb, arrays["rgb"].numpy())
+    assert hit.dtype == np.float64 and np.array_equal(hit, np.ones(7))
+    assert t.dtype == np.float64 and np.array_equal(t, arrays["t"].numpy())
+    assert not any(v["sampled"] for v in info.values()) and info["rgb"]["shape"] == [10, 100, 3]
+
+    budget = 6000
+    for run in ("a", "b"):
+        info = bench.dump_outputs(str(tmp_path / run), arrays, budget=budget)
+        assert all(v["sampled"] for v in info.values())
+        assert sum(p.stat().st_size for p in (tmp_path / run).iterdir()) <= budget
+    a, b = np.load(tmp_path / "a" / "rgb.npy"), np.load(tmp_path / "b" / "rgb.npy")
+    assert a.ndim == 1 and 0 < a.size < 3000 and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and np.all(np.isin(a, arrays["rgb"].numpy()))   # distinct elements, in the arrays' order

@@ -106,7 +106,7 @@ def test_bench_strong_scaling_dry_run(gpu, gather):
     """bench.py --scaling strong at world 2 (gloo, both ranks on the one GPU): a step is the whole 8-camera sheet
     (datasetgenerator.py:517-519), four cameras per rank, ONE tile gather per sheet (all-gather, or gather to rank 0)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--backend", "gloo", "--width", "160", "--height", "160", "--no-cpu-baseline", "--no-alt-precision", "--scaling", "strong",
            "--gather", gather]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
@@ -125,7 +125,7 @@ def test_bench_strong_scaling_dry_run(gpu, gather):
 
 def test_bench_strong_scaling_single_gpu(gpu):
     """The N = 1 point of the strong-scaling curve: all eight cameras on one GPU, no exchange."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--width", "160", "--height", "160",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--width", "160", "--height", "160",
            "--no-cpu-baseline", "--no-alt-precision", "--no-others", "--no-traffic", "--scaling", "strong"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -142,3 +142,50 @@ def test_bench_strong_scaling_single_gpu(gpu):
     # r06: the issue roof is priced per opcode class (2 / 4 / 8 cycles); with it the L1 gather path is the largest busy fraction
     assert d["roofline"]["bound"] in ("l1-gather-issue", "simd-issue") and d["roofline"]["frac"] == max(d["roofline"]["simd_issue_frac"], d["roofline"]["l1_gather_issue_frac"], d["roofline"]["matrix_pipe_frac"])
     assert d["roofline"]["traffic"] is None and "not measured" in d["roofline"]["traffic_source"]
+
+
+def _bench_line(*args):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *args], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(gpu, tmp_path):
+    """A plain bench.py run (no --full) times its steps and prints the headline only; --dump-outputs writes what the LAST timed step
+    returned.  Every step of a run repeats the same renders, so "last" is checked twice: the line names the timed step the arrays came from
+    (= --steps), and in a whole-sheet step (--scaling strong) the render outputs are those of the step's last camera (7) while `tiles` holds
+    all eight.  Bit for bit the renders of the same cameras in this process (fixed inputs: weights seed 0, benchmark cameras)."""
+    import numpy as np
+
+    from signerf_amd import Cameras, scene
+
+    size = ["--width", "96", "--height", "96"]
+    d = _bench_line("--gpus", "1", "--steps", "5", "--warmup", "2", *size, "--dump-outputs", str(tmp_path / "weak"))
+    assert d["full"] is False and d["steps"] == 5 and d["unit"] == "ray-samples/s" and d["higher_is_better"] is True and d["dtype"]
+    assert abs(d["ms_per_step"] * 5 - d["timed_region_s"] * 1e3) < 1e-6 and abs(d["value"] - 96 * 96 * 64 * 5 / d["timed_region_s"]) / d["value"] < 1e-6
+    assert not {"kernel_ms", "roofline", "roofline_hbm", "roofline_mfma", "alt_precision", "others", "cpu_baseline", "traffic_in_run"} & set(d)
+    assert d["dumped_outputs"]["timed_step"] == 5
+    s = _bench_line("--gpus", "1", "--steps", "3", "--warmup", "1", *size, "--scaling", "strong", "--dump-outputs", str(tmp_path / "strong"))
+    assert s["dumped_outputs"]["timed_step"] == 3 and not any(a["sampled"] for a in s["dumped_outputs"]["arrays"].values())
+
+    cfg = scene.benchmark_config(64)
+    cfg.precision = "fp16x2"
+    model = cfg.setup()
+    model.load_state_dict(scene.synthetic_state_dict(cfg, seed=0), strict=False)
+    model = model.to(gpu).eval()
+    cams = Cameras(scene.benchmark_cameras(8)[:, :3], 96.0, 96.0, 48.0, 48.0, 96, 96).to(gpu)
+    want = [{k: v.cpu().numpy() for k, v in dict.items(model.get_outputs_for_camera_ray_bundle(cams[i].generate_rays(camera_indices=0, aabb_box=model.render_aabb)))}
+            for i in range(8)]
+    for run, line, cam in (("weak", d, 0), ("strong", s, 7)):
+        names = sorted(want[cam]) + (["tiles"] if run == "strong" else [])
+        assert sorted(p.name for p in (tmp_path / run).iterdir()) == sorted(k + ".npy" for k in names) == sorted(k + ".npy" for k in line["dumped_outputs"]["arrays"])
+        for k, v in want[cam].items():
+            got = np.load(tmp_path / run / f"{k}.npy")
+            assert got.dtype == np.float32 and np.array_equal(got, v, equal_nan=True), (run, k)
+    tiles = np.load(tmp_path / "strong" / "tiles.npy")
+    assert tiles.dtype == np.float32 and tiles.shape == (8, 96, 96, 4)
+    assert not np.array_equal(want[0]["rgb"], want[7]["rgb"])                     # the cameras differ: the check above tells them apart
+    for i in range(8):
+        assert np.array_equal(tiles[i], np.concatenate([want[i]["rgb"], want[i]["depth"]], axis=-1), equal_nan=True), i

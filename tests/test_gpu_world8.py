@@ -166,7 +166,7 @@ def test_bench_world8_dry_run(gpu, world, scaling):
     identified over the process group before the first render) and the post-run checks (per-rank one-launch times, the gathered tiles bit
     for bit against local renders)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--steps", "3", "--warmup", "1",
            "--backend", "gloo", "--width", "96", "--height", "96", "--no-cpu-baseline", "--no-alt-precision", "--scaling", scaling]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 for s in "${@:-64 128 200 256 320 400 512 560 640 800 1024}"; do
   for sp in 1 0; do
-    SN_TAIL_SPLIT=$sp python bench.py --width $s --height $s --frames-in-flight 1 --steps 200 --warmup 20 --no-cpu-baseline --no-alt-precision 2>/dev/null | \
+    SN_TAIL_SPLIT=$sp python bench.py --full --width $s --height $s --frames-in-flight 1 --steps 200 --warmup 20 --no-cpu-baseline --no-alt-precision 2>/dev/null | \
       python -c "import json,sys; d=json.loads(sys.stdin.read()); print('size $s split $sp: frame period', round(d['ms_per_step'],4), 'ms; per-launch median', round(d['kernel_ms']['median'],4), 'p05', round(d['kernel_ms']['p05'],4))"
   done
 done
