@@ -1,6 +1,7 @@
 // sn_api.hip -- C ABI of libsignerf_hip.so (see include/signerf_hip.h for the contract and the
 // reference interfaces each entry point stands in for).  gfx950 only.
 #include "../../include/signerf_hip.h"
+#include "../../include/signerf_hip_mesh.h"
 
 #include <hip/hip_runtime.h>
 
@@ -19,6 +20,7 @@
 #include "sn_device.h"
 #include "sn_main.h"
 #include "sn_mask.h"
+#include "sn_mesh.h"
 #include "sn_normals.h"
 #include "sn_proposal.h"
 #include "sn_stage.h"
@@ -2226,30 +2228,15 @@ size_t sn_mask_workspace_bytes(int32_t height, int32_t width) {
     return align256(n) + align256((size_t)height * (width + 1) * 4) + 256;
 }
 
-int sn_aabb_mask_condition(const float* origins, const float* directions, const float* depth, int32_t height, int32_t width,
-                           const float* aabb, const SnMaskOpts* opts, uint8_t* mask, float* condition, void* workspace,
-                           size_t workspace_bytes, SnStream stream) {
-    if (!origins || !directions || !depth || !aabb || !opts || !mask || height <= 0 || width <= 0)
-        return fail(nullptr, SN_ERR_INVALID, "sn_aabb_mask_condition: bad argument");
-    SnMaskOpts opts_own;
-    if (int rc = adopt_struct(nullptr, opts, kMaskOptsMin, opts_own, "sn_aabb_mask_condition: SnMaskOpts")) return rc;
-    opts = &opts_own;
-    if (opts->dilate_w < 0 || opts->dilate_h < 0 || opts->dilate_w > SN_MASK_MAX_K || opts->dilate_h > SN_MASK_MAX_K ||
-        ((opts->dilate_w == 0) != (opts->dilate_h == 0)))
-        return fail(nullptr, SN_ERR_INVALID, "sn_aabb_mask_condition: dilation size must be 0 or within [1," + std::to_string(SN_MASK_MAX_K) + "] in both dimensions");
-    if (!workspace || workspace_bytes < sn_mask_workspace_bytes(height, width))
-        return fail(nullptr, SN_ERR_WORKSPACE, "sn_aabb_mask_condition: workspace too small");
-    clear_stamp(workspace);  // (a caller may hand the mask step the memory a render used: its bins are gone then)
-    hipStream_t st = (hipStream_t)stream;
+// The part of SnMaskParams both masking modes share: options (opts already adopted and validated), the elliptical element, the
+// workspace carve-up (sn_mask_workspace_bytes) and the outputs.
+static void fill_mask_params(const SnMaskOpts* opts, const float* depth, int32_t height, int32_t width, void* workspace, uint8_t* mask,
+                             float* condition, SnMaskParams& p) {
     const size_t n = (size_t)height * width;
-    SnMaskParams p;
     memset(&p, 0, sizeof(p));
-    p.origins = origins;
-    p.directions = directions;
     p.depth = depth;
     p.height = height;
     p.width = width;
-    memcpy(p.aabb, aabb, sizeof(p.aabb));
     p.inverse_mask = opts->inverse_mask;
     p.dilate = opts->dilate_w > 0;
     if (p.dilate) {
@@ -2287,6 +2274,29 @@ int sn_aabb_mask_condition(const float* origins, const float* directions, const 
     p.stats = (uint32_t*)(ws + align256(n) + align256((size_t)height * (width + 1) * 4));
     p.mask = mask;
     p.condition = condition;
+}
+
+int sn_aabb_mask_condition(const float* origins, const float* directions, const float* depth, int32_t height, int32_t width,
+                           const float* aabb, const SnMaskOpts* opts, uint8_t* mask, float* condition, void* workspace,
+                           size_t workspace_bytes, SnStream stream) {
+    if (!origins || !directions || !depth || !aabb || !opts || !mask || height <= 0 || width <= 0)
+        return fail(nullptr, SN_ERR_INVALID, "sn_aabb_mask_condition: bad argument");
+    SnMaskOpts opts_own;
+    if (int rc = adopt_struct(nullptr, opts, kMaskOptsMin, opts_own, "sn_aabb_mask_condition: SnMaskOpts")) return rc;
+    opts = &opts_own;
+    if (opts->dilate_w < 0 || opts->dilate_h < 0 || opts->dilate_w > SN_MASK_MAX_K || opts->dilate_h > SN_MASK_MAX_K ||
+        ((opts->dilate_w == 0) != (opts->dilate_h == 0)))
+        return fail(nullptr, SN_ERR_INVALID, "sn_aabb_mask_condition: dilation size must be 0 or within [1," + std::to_string(SN_MASK_MAX_K) + "] in both dimensions");
+    if (!workspace || workspace_bytes < sn_mask_workspace_bytes(height, width))
+        return fail(nullptr, SN_ERR_WORKSPACE, "sn_aabb_mask_condition: workspace too small");
+    clear_stamp(workspace);  // (a caller may hand the mask step the memory a render used: its bins are gone then)
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)height * width;
+    SnMaskParams p;
+    fill_mask_params(opts, depth, height, width, workspace, mask, condition, p);
+    p.origins = origins;
+    p.directions = directions;
+    memcpy(p.aabb, aabb, sizeof(p.aabb));
     hipError_t e = hipMemsetAsync(p.stats, 0, 4, st);
     if (e == hipSuccess) e = hipMemsetAsync(p.stats + 1, 0xff, 4, st);
     if (e == hipSuccess) e = hipMemsetAsync(p.stats + 2, 0, 4, st);
@@ -2296,6 +2306,95 @@ int sn_aabb_mask_condition(const float* origins, const float* directions, const 
     hipLaunchKernelGGL(sn_mask_condition_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_aabb_mask_condition launch: ") + hipGetErrorString(e));
+    return SN_OK;
+}
+
+
+// ---- include/signerf_hip_mesh.h: the "shape" masking mode ---------------------------------------------------------------------------
+int sn_mesh_abi_version(void) { return SN_MESH_ABI_VERSION; }
+
+constexpr size_t kMeshRasterOptsMin = sizeof(SnMeshRasterOpts);  // the first layout
+#define SN_MESH_MAX_DIM 16384               // the tile records pack pixel coordinates into 16 bits
+#define SN_MESH_MAX_TRIS ((int64_t)1 << 30)  // int32 triangle indexing in the kernels, with room for a batch past the end
+
+size_t sn_mesh_workspace_bytes(int64_t n_triangles, int32_t height, int32_t width) {
+    if (n_triangles < 0 || n_triangles > SN_MESH_MAX_TRIS || height <= 0 || width <= 0 || height > SN_MESH_MAX_DIM || width > SN_MESH_MAX_DIM)
+        return 0;
+    const size_t f = (size_t)n_triangles;
+    return align256(f * sizeof(SnMeshTri)) + align256(f * sizeof(uint2)) + 256;
+}
+
+int sn_mesh_raster_depth(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, const float* model_view,
+                         float fx, float fy, float cx, float cy, int32_t height, int32_t width, const SnMeshRasterOpts* opts, float* depth,
+                         void* workspace, size_t workspace_bytes, SnStream stream) {
+    if (!model_view || !opts || !depth || n_vertices < 0 || n_triangles < 0 || n_triangles > SN_MESH_MAX_TRIS || height <= 0 || width <= 0 ||
+        height > SN_MESH_MAX_DIM || width > SN_MESH_MAX_DIM || (n_triangles > 0 && (!vertices || !triangles || n_vertices == 0)))
+        return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_depth: bad argument");
+    SnMeshRasterOpts o;
+    if (int rc = adopt_struct(nullptr, opts, kMeshRasterOptsMin, o, "sn_mesh_raster_depth: SnMeshRasterOpts")) return rc;
+    if (!(o.znear > 0.0f) || !(o.zfar > o.znear) || !std::isfinite(o.zfar))
+        return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_depth: need 0 < znear < zfar < inf");
+    if (!(fx != 0.0f) || !(fy != 0.0f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+        return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_depth: intrinsics must be finite with fx, fy != 0");
+    if (!workspace || workspace_bytes < sn_mesh_workspace_bytes(n_triangles, height, width))
+        return fail(nullptr, SN_ERR_WORKSPACE, "sn_mesh_raster_depth: workspace too small");
+    clear_stamp(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    SnMeshRasterParams p;
+    memset(&p, 0, sizeof(p));
+    p.vertices = vertices;
+    p.tris = triangles;
+    p.n_vertices = n_vertices;
+    p.n_tris = (int32_t)n_triangles;
+    memcpy(p.mv, model_view, sizeof(p.mv));
+    p.fx = fx;
+    p.fy = fy;
+    p.cx = cx;
+    p.cy = cy;
+    p.height = height;
+    p.width = width;
+    p.znear = o.znear;
+    p.zfar = o.zfar;
+    p.cull = o.cull_back_faces != 0;
+    char* ws = (char*)workspace;
+    p.rec = (SnMeshTri*)ws;
+    p.bbox = (uint2*)(ws + align256((size_t)n_triangles * sizeof(SnMeshTri)));
+    p.depth = depth;
+    if (n_triangles > 0) hipLaunchKernelGGL(sn_mesh_setup_kernel, dim3((unsigned)((n_triangles + 255) / 256)), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(sn_mesh_tile_kernel, dim3((unsigned)((width + SN_MESH_TILE - 1) / SN_MESH_TILE), (unsigned)((height + SN_MESH_TILE - 1) / SN_MESH_TILE)),
+                       dim3(SN_MESH_BATCH), 0, st, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_mesh_raster_depth launch: ") + hipGetErrorString(e));
+    return SN_OK;
+}
+
+int sn_shape_mask_condition(const float* mesh_depth, const float* nerf_depth, int32_t height, int32_t width, const SnMaskOpts* opts,
+                            uint8_t* mask, float* condition, void* workspace, size_t workspace_bytes, SnStream stream) {
+    if (!mesh_depth || !nerf_depth || !opts || !mask || height <= 0 || width <= 0)
+        return fail(nullptr, SN_ERR_INVALID, "sn_shape_mask_condition: bad argument");
+    SnMaskOpts opts_own;
+    if (int rc = adopt_struct(nullptr, opts, kMaskOptsMin, opts_own, "sn_shape_mask_condition: SnMaskOpts")) return rc;
+    opts = &opts_own;
+    if (opts->dilate_w < 0 || opts->dilate_h < 0 || opts->dilate_w > SN_MASK_MAX_K || opts->dilate_h > SN_MASK_MAX_K ||
+        ((opts->dilate_w == 0) != (opts->dilate_h == 0)))
+        return fail(nullptr, SN_ERR_INVALID, "sn_shape_mask_condition: dilation size must be 0 or within [1," + std::to_string(SN_MASK_MAX_K) + "] in both dimensions");
+    if (!workspace || workspace_bytes < sn_mask_workspace_bytes(height, width))
+        return fail(nullptr, SN_ERR_WORKSPACE, "sn_shape_mask_condition: workspace too small");
+    clear_stamp(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)height * width;
+    SnShapeMaskParams sp;
+    fill_mask_params(opts, nerf_depth, height, width, workspace, mask, condition, sp.m);
+    sp.mesh_depth = mesh_depth;
+    hipError_t e = hipMemsetAsync(sp.m.stats, 0, 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(sp.m.stats + 1, 0xff, 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(sp.m.stats + 2, 0, 4, st);
+    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_shape_mask_condition memset: ") + hipGetErrorString(e));
+    hipLaunchKernelGGL(sn_shape_visible_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, SN_MASK_VIS_BLOCKS)), dim3(256), 0, st, sp);
+    if (sp.m.dilate) hipLaunchKernelGGL(sn_mask_prefix_kernel, dim3((unsigned)height), dim3(64), 0, st, sp.m);
+    hipLaunchKernelGGL(sn_shape_condition_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sp);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_shape_mask_condition launch: ") + hipGetErrorString(e));
     return SN_OK;
 }
 

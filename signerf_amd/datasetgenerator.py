@@ -7,7 +7,10 @@ reference moves the mask to the CPU for ``cv2.dilate`` (:776-778) and synchronis
 (:770); here the slab test, the mask, the elliptical dilation, the masked depth min/max and the condition image are three
 small kernels behind ``sn_aabb_mask_condition`` and nothing leaves the device.
 
-``masking_mode="shape"`` needs the OpenGL mesh rasteriser (signerf/renderer, out of scope) and raises.
+``masking_mode="shape"`` (:711-754): the proxy mesh of ``DatasetGeneratorConfig.renderer`` (the bunny by default) is rasterised to a
+z-depth image by ``sn_mesh_raster_depth`` (``renderer.Renderer``; the reference draws it with pyrender on OpenGL), and
+``sn_shape_mask_condition`` builds the mask and the condition from the mesh depth and the NeRF depth -- again without a host round trip.
+``combine_shape_with_depth`` (aabb mode with the mesh's shaded colour) is not built: the flag is carried and has no effect.
 """
 
 from __future__ import annotations
@@ -23,12 +26,14 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from .renderer import Renderer, RendererConfig
 
 
 @dataclass
 class DatasetGeneratorConfig:
-    """The fields of the reference's DatasetGeneratorConfig (datasetgenerator.py:32-81) except the two sub-configs of components that are
-    out of scope (``renderer``: the OpenGL mesh rasteriser; ``diffuser``: the HTTP client -- ``DatasetGenerator`` takes a callable)."""
+    """The fields of the reference's DatasetGeneratorConfig (datasetgenerator.py:32-81) except the sub-config of a component that is out
+    of scope (``diffuser``: the HTTP client -- ``DatasetGenerator`` takes a callable).  ``renderer`` (the proxy mesh of the shape masking
+    mode) is ``None`` by default, which means the reference's ``RendererConfig()`` defaults; it is left out of config.yml while None."""
 
     path: Path = field(default_factory=lambda: Path("./generations"))
     dataset_name: str = field(default_factory=lambda: "experiment-" + datetime.datetime.now().strftime("%Y%m%d-%H%M%S"))
@@ -49,7 +54,8 @@ class DatasetGeneratorConfig:
     border_width_between_images: int = 0
     inverse_mask: bool = False
     manual_depth: Optional[Tuple[float, float]] = None
-    combine_shape_with_depth: bool = False   # shape mode only (mesh rasteriser, out of scope); carried for signature parity
+    combine_shape_with_depth: bool = False   # aabb mode + the mesh's shaded colour: not built, carried for signature parity
+    renderer: Optional[RendererConfig] = None
 
 
 def aabb_mask_and_condition(depth: Tensor, rays_o: Tensor, rays_d: Tensor, aabb: Tensor, mask_dialation: Optional[Tuple[int, int]] = (50, 50),
@@ -82,9 +88,41 @@ def aabb_mask_and_condition(depth: Tensor, rays_o: Tensor, rays_d: Tensor, aabb:
     return mask.bool(), cond
 
 
-def render_camera(config: DatasetGeneratorConfig, graph, camera, with_mask: bool = True, with_condition: bool = True):
-    """One camera: rgb, mask, condition (datasetgenerator.py:677-820, aabb mode).  `camera`: a 0-dim ``Cameras`` of this package or
-    any object with nerfstudio's camera accessors (adopted: ray generation always runs in the HIP kernel)."""
+def shape_mask_and_condition(mesh_depth: Tensor, depth: Tensor, mask_dialation: Optional[Tuple[int, int]] = (50, 50), inverse_mask: bool = False,
+                             manual_depth: Optional[Tuple[float, float]] = None, additional_depth_radius: float = 0.1, with_condition: bool = True):
+    """datasetgenerator.py:716-754 on the GPU.  mesh_depth (the proxy mesh's z-depth, 0 = not drawn) and depth (the NeRF's) [H,W,1] ->
+    (mask [H,W,1] bool, condition [H,W,1] fp32 | None).  If nothing is visible both are all-zero, as in the reference; if something is
+    visible but no visible pixel has a mesh depth > 0 (inverse_mask; the reference raises there) the condition is all-zero."""
+    lib = _lib.load()
+    H, W = depth.shape[0], depth.shape[1]
+    dev = depth.device
+    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+    md, z = f32(mesh_depth), f32(depth)
+    if md.numel() != H * W or z.numel() != H * W:
+        raise ValueError(f"mesh depth {tuple(mesh_depth.shape)} and NeRF depth {tuple(depth.shape)} must both be [H,W,1]")
+    opts = _lib.SnMaskOpts()
+    opts.inverse_mask = int(bool(inverse_mask))
+    if mask_dialation is not None:
+        opts.dilate_w, opts.dilate_h = int(mask_dialation[0]), int(mask_dialation[1])
+    opts.has_manual_depth = int(manual_depth is not None)
+    if manual_depth is not None:
+        opts.manual_min, opts.manual_max = float(manual_depth[0]), float(manual_depth[1])
+    opts.additional_depth_radius = float(additional_depth_radius)
+    with torch.cuda.device(dev):
+        mask = torch.empty((H, W, 1), dtype=torch.uint8, device=dev)
+        cond = torch.empty((H, W, 1), dtype=torch.float32, device=dev) if with_condition else None
+        ws = torch.empty(lib.sn_mask_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
+        _lib.check(lib.sn_shape_mask_condition(_lib.ptr(md), _lib.ptr(z), H, W, C.byref(opts), _lib.ptr(mask), _lib.ptr(cond), ws.data_ptr(),
+                                               ws.numel(), _lib.current_stream()),
+                   None, "sn_shape_mask_condition")
+    return mask.bool(), cond
+
+
+def render_camera(config: DatasetGeneratorConfig, graph, camera, with_mask: bool = True, with_condition: bool = True,
+                  renderer: Optional[Renderer] = None):
+    """One camera: rgb, mask, condition (datasetgenerator.py:677-820).  `camera`: a 0-dim ``Cameras`` of this package or any object with
+    nerfstudio's camera accessors (adopted: ray generation always runs in the HIP kernel).  ``masking_mode="shape"`` needs `renderer`
+    (a ``renderer.Renderer`` after ``setup()``), as the reference needs ``self.renderer``."""
     camera = _adopt(camera)
     camera_ray_bundle = camera.generate_rays(camera_indices=0, aabb_box=graph.render_aabb)
     graph.eval()
@@ -95,8 +133,17 @@ def render_camera(config: DatasetGeneratorConfig, graph, camera, with_mask: bool
     rgb, depth = outputs["rgb"], outputs["depth"]
     if not with_mask:
         return rgb, None, None, None  # the reference's 4-tuple early exit (:708)
+    if config.masking_mode == "shape":
+        if renderer is None:
+            raise ValueError("Renderer is None but masking mode is shape")
+        _, mesh_depth = renderer.render_camera(camera)
+        mask, cond = shape_mask_and_condition(mesh_depth, depth, config.mask_dialation, config.inverse_mask, config.manual_depth,
+                                              config.additional_depth_radius, with_condition)
+        if not with_condition:
+            return rgb, mask, None, None
+        return rgb, mask, cond
     if config.masking_mode != "aabb":
-        raise NotImplementedError("masking_mode='shape' needs the OpenGL mesh rasteriser (signerf/renderer), which is out of scope")
+        raise NotImplementedError(f"masking_mode={config.masking_mode!r}: the reference knows 'aabb' and 'shape'")
     aabb = torch.tensor([config.aabb_min, config.aabb_max], dtype=torch.float32)
     mask, cond = aabb_mask_and_condition(depth, camera_ray_bundle.origins, camera_ray_bundle.directions, aabb, config.mask_dialation,
                                          config.inverse_mask, config.manual_depth, config.additional_depth_radius, with_condition)
@@ -248,7 +295,7 @@ def _camera_key(camera) -> bytes:
 
 
 class DatasetGenerator:
-    """``DatasetGenerator`` of the reference for ``masking_mode="aabb"``: same constructor arguments, attributes and methods
+    """``DatasetGenerator`` of the reference for both masking modes: same constructor arguments, attributes and methods
     (``init_directory``, ``generate_dataset``, ``save_generated_images``, ``generate_reference_sheet``,
     ``generate_with_reference_sheet``, ``render_camera``), the same files on disk.
 
@@ -289,6 +336,8 @@ class DatasetGenerator:
         self.rows, self.cols = config.rows, config.cols
         self.border_width_between_images = config.border_width_between_images
         self.mask_dialation, self.additional_depth_radius, self.manual_depth = config.mask_dialation, config.additional_depth_radius, config.manual_depth
+        # the proxy mesh of the shape mode; set up (mesh parsed) at the start of generate_dataset, as the reference does at :226
+        self.renderer = Renderer(config.renderer or RendererConfig(), device=device) if self.masking_mode == "shape" else None
         self.diffuse = diffuse or identity_diffuse
         self.group = group
         if save_workers is None:  # PNG encoding is the slowest stage of the loop: spread it over the host's cores (dataset_io.encode_png releases the GIL)
@@ -340,7 +389,8 @@ class DatasetGenerator:
         import yaml
 
         # the reference dumps its config OBJECT (a yaml python/object tag of its own class); here the same fields as a plain mapping
-        plain = {k: (str(v) if isinstance(v, Path) else (list(v) if isinstance(v, tuple) else v)) for k, v in dataclasses.asdict(self.config).items()}
+        plain = {k: (str(v) if isinstance(v, Path) else (list(v) if isinstance(v, tuple) else v)) for k, v in dataclasses.asdict(self.config).items()
+                 if not (k == "renderer" and v is None)}
         (self.dataset_path / "config.yml").write_text(yaml.safe_dump(plain), "utf8")
 
     # -- the pre-computed render stage -------------------------------------------------------------------------------------
@@ -352,17 +402,29 @@ class DatasetGenerator:
         t0 = time.perf_counter()
         rank, world = self._dist()
         tiles = sheet.render_views(graph, cameras, self.config, group=self.group, dst=0 if world > 1 else None,
-                                   render_camera_fn=lambda cfg, g, cam: render_camera(cfg, g, cam))
+                                   render_camera_fn=lambda cfg, g, cam: self._render_module_fn(cfg, g, cam))
         if tiles is not None:
             for i, cam in enumerate(cameras):
                 self._views[_camera_key(cam)] = (tiles, i)
         self._tick("render_s", t0)
 
+    def _ready_renderer(self) -> Optional[Renderer]:
+        if self.renderer is not None and self.renderer.pose is None:
+            self.renderer.setup()
+        return self.renderer
+
+    def _render_module_fn(self, config, graph, camera, with_mask: bool = True, with_condition: bool = True):
+        # the module-level render_camera, looked up at call time; `renderer` is only passed in shape mode, so an aabb run calls it exactly
+        # as before
+        if self.renderer is None:
+            return render_camera(config, graph, camera, with_mask, with_condition)
+        return render_camera(config, graph, camera, with_mask, with_condition, renderer=self._ready_renderer())
+
     def render_camera(self, graph, camera, with_mask: bool = True, with_condition: bool = True, combine_shape_with_depth: bool = False):
-        """datasetgenerator.py:677-820 (aabb mode): a pre-computed view when there is one, else rendered now."""
+        """datasetgenerator.py:677-820: a pre-computed view when there is one, else rendered now."""
         hit = self._views.get(_camera_key(camera)) if (with_mask and with_condition) else None
         if hit is None:
-            return render_camera(self.config, graph, camera, with_mask, with_condition)
+            return self._render_module_fn(self.config, graph, camera, with_mask, with_condition)
         tiles, i = hit
         return tiles[i, :, :, 0:3].contiguous(), tiles[i, :, :, 3:4] > 0.5, tiles[i, :, :, 4:5].contiguous()
 
@@ -403,6 +465,8 @@ class DatasetGenerator:
             raise ValueError("Original dataset and camera_to_worlds must be given to merge with original dataset")
         rank, world = self._dist()
         self.timings = {}
+        if self.renderer is not None:
+            self.renderer.setup()   # :226 (a missing or malformed mesh raises here, before anything is rendered)
         if synthetic_camera_to_worlds is not None:
             self.is_synthetic = True
         scaled_image_width = int(self.width // self.downscale_factor)

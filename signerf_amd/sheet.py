@@ -261,16 +261,19 @@ def _default_device():
 
 
 def render_views(model, cameras, generator_config, group=None, frames_in_flight: int = 2, dst: Optional[int] = None,
-                 render_camera_fn=None) -> Optional[Tensor]:
+                 render_camera_fn=None, renderer=None) -> Optional[Tensor]:
     """BASELINE.json configs[4]: the per-view work of the dataset-generator loops
     (/root/reference/signerf/datasetgenerator/datasetgenerator.py:331-338 and :517-519): for every camera, render ->
-    mask -> condition (``render_camera``, aabb mode), sharded round-robin over the ranks, tiles all-gathered (``dst``: gathered to
-    that rank only).
+    mask -> condition (``render_camera``, either masking mode; ``renderer``: the set-up ``renderer.Renderer`` the shape mode needs), sharded
+    round-robin over the ranks, tiles all-gathered (``dst``: gathered to that rank only).
     -> [n_cameras, H, W, 5] = rgb (3) ++ mask (1, 0/1) ++ condition (1) on every rank.  The diffusion call that follows
     each view in the reference is a remote HTTP service and stays where it is (rank 0)."""
     from . import datasetgenerator
 
-    render_camera = render_camera_fn or datasetgenerator.render_camera
+    if render_camera_fn is None:
+        render_camera = lambda cfg, g, cam: datasetgenerator.render_camera(cfg, g, cam, renderer=renderer)  # noqa: E731
+    else:
+        render_camera = render_camera_fn
 
     def render_fn(i: int):
         rgb, mask, cond = render_camera(generator_config, model, cameras[i])

@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""Shape masking mode cost per view: proxy-mesh raster (sn_mesh_raster_depth) + shape mask / condition (sn_shape_mask_condition) at
+800 x 800, beside the 800 x 800 x 64-sample NeRF render of the same view (scene.benchmark_config(64), the bench.py workload).  Times are
+hipEvent intervals on the stream, median of --reps after --warmup.
+
+Meshes (tests/mesh_oracle.py's procedural icosphere restated here: tools do not import the tests):
+  bunny_5120    a 5 120-face icosphere of radius 0.15 at the origin (bunny-sized: the bunny has 4 968 faces), seen from the
+                benchmark cameras (views 0, 2, 4, 6 of circle_poses(8), radius 0.5)
+  closeup_5120  the same mesh 0.12 in front of the camera: its triangles cover large parts of the frame
+  big_1.3M      a 1 310 720-face icosphere in the bunny's place
+
+    python tools/shape_mask_bench.py [--size 800] [--reps 50] [--json OUT]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from signerf_amd import Cameras, scene  # noqa: E402
+from signerf_amd.datasetgenerator import shape_mask_and_condition  # noqa: E402
+from signerf_amd.renderer import RendererConfig, model_view, object_pose, raster_depth  # noqa: E402
+
+
+def icosphere(subdivisions):
+    t = (1.0 + 5 ** 0.5) / 2.0
+    v = np.array([[-1, t, 0], [1, t, 0], [-1, -t, 0], [1, -t, 0], [0, -1, t], [0, 1, t], [0, -1, -t], [0, 1, -t],
+                  [t, 0, -1], [t, 0, 1], [-t, 0, -1], [-t, 0, 1]], dtype=np.float64)
+    f = np.array([[0, 11, 5], [0, 5, 1], [0, 1, 7], [0, 7, 10], [0, 10, 11], [1, 5, 9], [5, 11, 4], [11, 10, 2], [10, 7, 6], [7, 1, 8],
+                  [3, 9, 4], [3, 4, 2], [3, 2, 6], [3, 6, 8], [3, 8, 9], [4, 9, 5], [2, 4, 11], [6, 2, 10], [8, 6, 7], [9, 8, 1]])
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    tri = v[f]
+    for _ in range(subdivisions):
+        a, b, c = tri[:, 0], tri[:, 1], tri[:, 2]
+        ab, bc, ca = a + b, b + c, c + a
+        for m in (ab, bc, ca):
+            m /= np.linalg.norm(m, axis=1, keepdims=True)
+        tri = np.stack([np.stack([a, ab, ca], 1), np.stack([ab, b, bc], 1), np.stack([ca, bc, c], 1), np.stack([ab, bc, ca], 1)], 1).reshape(-1, 3, 3)
+    verts = tri.reshape(-1, 3).astype(np.float32)
+    return verts, np.arange(verts.shape[0], dtype=np.int32).reshape(-1, 3)
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return float(np.median([a.elapsed_time(b) for a, b in ev]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=800)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--nerf-reps", type=int, default=10)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    S = a.size
+    cfg = scene.benchmark_config(64)
+    model = cfg.setup()
+    model.load_state_dict(scene.synthetic_state_dict(cfg, seed=0), strict=False)
+    model = model.to(dev).eval()
+    c2w = scene.benchmark_cameras(8)[:, :3]
+    cams = Cameras(c2w, 1.2 * S, 1.2 * S, S / 2, S / 2, S, S).to(dev)
+    pose = object_pose(RendererConfig(scale=[0.015, 0.015, 0.015]))   # radius 0.15, about the bunny's extent at the default scale
+    meshes = {"bunny_5120": icosphere(4), "big_1.3M": icosphere(8)}
+    rows = []
+    for view in range(0, 8, 2):
+        cam = cams[view]
+        bundle = cam.generate_rays(0, aabb_box=model.render_aabb)
+        nerf_ms = timed(lambda: model.get_outputs_for_camera_ray_bundle(bundle), a.nerf_reps, 2)
+        nerf_depth = model.get_outputs_for_camera_ray_bundle(bundle)["depth"]
+        host = cam._host[0].tolist()
+        legs = [("bunny_5120", model_view(host[:12], pose)), ("big_1.3M", model_view(host[:12], pose))]
+        # close-up: the same mesh 0.12 in front of the camera (radius 0.15: the camera sits just outside it, the frame is mostly mesh)
+        close = model_view(host[:12], pose).copy()
+        close[:, 3] = [0.0, 0.0, -0.27]
+        legs.append(("closeup_5120", close))
+        for name, mv in legs:
+            v, f = meshes["big_1.3M" if name.startswith("big") else "bunny_5120"]
+            vt, ft = torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev)
+            depth = torch.empty((S, S, 1), device=dev)
+            r_ms = timed(lambda: raster_depth(vt, ft, mv, host[12], host[13], host[14], host[15], S, S, out=depth), a.reps, a.warmup)
+            m_ms = timed(lambda: shape_mask_and_condition(depth, nerf_depth), a.reps, a.warmup)
+            cover = float((depth > 0).float().mean())
+            rows.append({"view": view, "mesh": name, "faces": int(f.shape[0]), "raster_ms": round(r_ms, 4), "mask_ms": round(m_ms, 4),
+                         "raster_plus_mask_ms": round(r_ms + m_ms, 4), "nerf_render_ms": round(nerf_ms, 3),
+                         "share_of_render": round((r_ms + m_ms) / nerf_ms, 4), "mesh_coverage": round(cover, 4)})
+            print(json.dumps(rows[-1]), flush=True)
+    summary = {}
+    for name in ("bunny_5120", "closeup_5120", "big_1.3M"):
+        rs = [r for r in rows if r["mesh"] == name]
+        summary[name] = {k: float(np.median([r[k] for r in rs])) for k in ("raster_ms", "mask_ms", "raster_plus_mask_ms", "nerf_render_ms",
+                                                                             "share_of_render", "mesh_coverage")}
+    out = {"size": S, "reps": a.reps, "gpu": torch.cuda.get_device_name(0), "median_over_views": summary, "rows": rows}
+    print(json.dumps({"median_over_views": summary}))
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
