@@ -15,6 +15,7 @@ SN_MAX_PROPOSALS = 2
 SN_OK, SN_ERR_INVALID, SN_ERR_HIP, SN_ERR_STATE, SN_ERR_WORKSPACE = 0, 1, 2, 3, 4
 SN_ABI_VERSION = 6   # include/signerf_hip.h "ABI evolution": load() refuses a library built with another one
 SN_MESH_ABI_VERSION = 1   # include/signerf_hip_mesh.h, checked the same way
+SN_MESH_COLOR_ABI_VERSION = 1   # include/signerf_hip_mesh_color.h, checked the same way
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # SIGNERF_HIP_LIB: load another build of the library (A/B experiments with tools/ab_lib.py); the default is the in-tree build
@@ -203,6 +204,30 @@ MESH_SIGNATURES = {
                                           C.c_void_p]),
 }
 
+
+
+class SnMeshShadeOpts(_Sized):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("base_color", C.c_float * 4),
+        ("ambient", C.c_float * 3),
+        ("background", C.c_float * 3),
+        ("gamma", C.c_int32),
+    ]
+
+
+# The companion header include/signerf_hip_mesh_color.h (the mesh's colour image, aabb mode with combine_shape_with_depth): every symbol it
+# declares (tests/test_mesh_color_host.py checks them).
+MESH_COLOR_SIGNATURES = {
+    "sn_mesh_color_abi_version": (C.c_int, []),
+    "sn_mesh_color_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "sn_mesh_raster_color": (C.c_int, [_FP, C.c_int64, _FP, _FP, C.c_int64, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float,
+                                       C.c_int32, C.c_int32, C.POINTER(SnMeshRasterOpts), C.POINTER(SnMeshShadeOpts), _FP, _FP, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
+    "sn_aabb_mask_condition_combined": (C.c_int, [_FP, _FP, _FP, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(SnMaskOpts), _FP, _FP,
+                                                  _FP, _FP, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lock = threading.Lock()
 
@@ -226,7 +251,7 @@ def load() -> C.CDLL:
             lib = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover
             raise SignerfHipError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in list(SIGNATURES.items()) + list(MESH_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(MESH_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items()):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise SignerfHipError(f"{LIB_PATH} does not export {name}: it was built from another include/signerf_hip.h -- rebuild it "
@@ -240,6 +265,10 @@ def load() -> C.CDLL:
         if got != SN_MESH_ABI_VERSION:
             raise SignerfHipError(f"{LIB_PATH} reports SN_MESH_ABI_VERSION {got}, this binding was written for {SN_MESH_ABI_VERSION}: "
                                   "rebuild the library")
+        got = lib.sn_mesh_color_abi_version()
+        if got != SN_MESH_COLOR_ABI_VERSION:
+            raise SignerfHipError(f"{LIB_PATH} reports SN_MESH_COLOR_ABI_VERSION {got}, this binding was written for "
+                                  f"{SN_MESH_COLOR_ABI_VERSION}: rebuild the library")
         _lib = lib
         return lib
 

@@ -2,6 +2,7 @@
 // reference interfaces each entry point stands in for).  gfx950 only.
 #include "../../include/signerf_hip.h"
 #include "../../include/signerf_hip_mesh.h"
+#include "../../include/signerf_hip_mesh_color.h"
 
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,7 @@
 #include "sn_main.h"
 #include "sn_mask.h"
 #include "sn_mesh.h"
+#include "sn_mesh_color.h"
 #include "sn_normals.h"
 #include "sn_proposal.h"
 #include "sn_stage.h"
@@ -2395,6 +2397,111 @@ int sn_shape_mask_condition(const float* mesh_depth, const float* nerf_depth, in
     hipLaunchKernelGGL(sn_shape_condition_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sp);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_shape_mask_condition launch: ") + hipGetErrorString(e));
+    return SN_OK;
+}
+
+
+// ---- include/signerf_hip_mesh_color.h: the mesh's colour image, aabb mode with combine_shape_with_depth ------------------------------
+int sn_mesh_color_abi_version(void) { return SN_MESH_COLOR_ABI_VERSION; }
+
+constexpr size_t kMeshShadeOptsMin = sizeof(SnMeshShadeOpts);  // the first layout
+
+size_t sn_mesh_color_workspace_bytes(int64_t n_triangles, int32_t height, int32_t width) {
+    return sn_mesh_workspace_bytes(n_triangles, height, width);
+}
+
+int sn_mesh_raster_color(const float* vertices, int64_t n_vertices, const uint8_t* vertex_colors, const int32_t* triangles,
+                         int64_t n_triangles, const float* model_view, float fx, float fy, float cx, float cy, int32_t height, int32_t width,
+                         const SnMeshRasterOpts* opts, const SnMeshShadeOpts* shade, float* depth, uint8_t* color, void* workspace,
+                         size_t workspace_bytes, SnStream stream) {
+    if (!model_view || !opts || !shade || !color || n_vertices < 0 || n_triangles < 0 || n_triangles > SN_MESH_MAX_TRIS || height <= 0 ||
+        width <= 0 || height > SN_MESH_MAX_DIM || width > SN_MESH_MAX_DIM || (n_triangles > 0 && (!vertices || !triangles || n_vertices == 0)))
+        return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_color: bad argument");
+    SnMeshRasterOpts o;
+    if (int rc = adopt_struct(nullptr, opts, kMeshRasterOptsMin, o, "sn_mesh_raster_color: SnMeshRasterOpts")) return rc;
+    SnMeshShadeOpts so;
+    if (int rc = adopt_struct(nullptr, shade, kMeshShadeOptsMin, so, "sn_mesh_raster_color: SnMeshShadeOpts")) return rc;
+    if (!(o.znear > 0.0f) || !(o.zfar > o.znear) || !std::isfinite(o.zfar))
+        return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_color: need 0 < znear < zfar < inf");
+    if (!(fx != 0.0f) || !(fy != 0.0f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+        return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_color: intrinsics must be finite with fx, fy != 0");
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(so.base_color[c]) || !std::isfinite(so.ambient[c]) || !std::isfinite(so.background[c]))
+            return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_color: base_color, ambient and background must be finite");
+    if (!workspace || workspace_bytes < sn_mesh_color_workspace_bytes(n_triangles, height, width))
+        return fail(nullptr, SN_ERR_WORKSPACE, "sn_mesh_raster_color: workspace too small");
+    clear_stamp(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    SnMeshColorParams cp;
+    memset(&cp, 0, sizeof(cp));
+    SnMeshRasterParams& p = cp.r;  // filled as sn_mesh_raster_depth fills it
+    p.vertices = vertices;
+    p.tris = triangles;
+    p.n_vertices = n_vertices;
+    p.n_tris = (int32_t)n_triangles;
+    memcpy(p.mv, model_view, sizeof(p.mv));
+    p.fx = fx;
+    p.fy = fy;
+    p.cx = cx;
+    p.cy = cy;
+    p.height = height;
+    p.width = width;
+    p.znear = o.znear;
+    p.zfar = o.zfar;
+    p.cull = o.cull_back_faces != 0;
+    char* ws = (char*)workspace;
+    p.rec = (SnMeshTri*)ws;
+    p.bbox = (uint2*)(ws + align256((size_t)n_triangles * sizeof(SnMeshTri)));
+    p.depth = depth;
+    cp.vertex_colors = vertex_colors;
+    for (int c = 0; c < 3; ++c) {
+        cp.base[c] = so.base_color[c];
+        cp.ambient[c] = so.ambient[c];
+        cp.background[c] = so.background[c];
+    }
+    cp.gamma = so.gamma != 0;
+    cp.color = color;
+    if (n_triangles > 0) hipLaunchKernelGGL(sn_mesh_setup_kernel, dim3((unsigned)((n_triangles + 255) / 256)), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(sn_mesh_tile_color_kernel, dim3((unsigned)((width + SN_MESH_TILE - 1) / SN_MESH_TILE), (unsigned)((height + SN_MESH_TILE - 1) / SN_MESH_TILE)),
+                       dim3(SN_MESH_BATCH), 0, st, cp);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_mesh_raster_color launch: ") + hipGetErrorString(e));
+    return SN_OK;
+}
+
+int sn_aabb_mask_condition_combined(const float* origins, const float* directions, const float* depth, int32_t height, int32_t width,
+                                    const float* aabb, const SnMaskOpts* opts, const float* mesh_depth, const uint8_t* mesh_color,
+                                    uint8_t* mask, float* condition, void* workspace, size_t workspace_bytes, SnStream stream) {
+    if (!origins || !directions || !depth || !aabb || !opts || !mesh_depth || !mesh_color || !mask || height <= 0 || width <= 0)
+        return fail(nullptr, SN_ERR_INVALID, "sn_aabb_mask_condition_combined: bad argument");
+    SnMaskOpts opts_own;
+    if (int rc = adopt_struct(nullptr, opts, kMaskOptsMin, opts_own, "sn_aabb_mask_condition_combined: SnMaskOpts")) return rc;
+    opts = &opts_own;
+    if (opts->dilate_w < 0 || opts->dilate_h < 0 || opts->dilate_w > SN_MASK_MAX_K || opts->dilate_h > SN_MASK_MAX_K ||
+        ((opts->dilate_w == 0) != (opts->dilate_h == 0)))
+        return fail(nullptr, SN_ERR_INVALID, "sn_aabb_mask_condition_combined: dilation size must be 0 or within [1," + std::to_string(SN_MASK_MAX_K) + "] in both dimensions");
+    if (!workspace || workspace_bytes < sn_mask_workspace_bytes(height, width))
+        return fail(nullptr, SN_ERR_WORKSPACE, "sn_aabb_mask_condition_combined: workspace too small");
+    clear_stamp(workspace);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n = (size_t)height * width;
+    SnCombinedMaskParams cp;
+    fill_mask_params(opts, depth, height, width, workspace, mask, condition, cp.m);
+    SnMaskParams& p = cp.m;
+    p.origins = origins;
+    p.directions = directions;
+    memcpy(p.aabb, aabb, sizeof(p.aabb));
+    cp.mesh_depth = mesh_depth;
+    cp.mesh_color = mesh_color;
+    hipError_t e = hipMemsetAsync(p.stats, 0, 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(p.stats + 1, 0xff, 4, st);
+    if (e == hipSuccess) e = hipMemsetAsync(p.stats + 2, 0, 4, st);
+    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_aabb_mask_condition_combined memset: ") + hipGetErrorString(e));
+    hipLaunchKernelGGL(sn_mask_visible_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, SN_MASK_VIS_BLOCKS)), dim3(256), 0, st, p);
+    if (p.dilate) hipLaunchKernelGGL(sn_mask_prefix_kernel, dim3((unsigned)height), dim3(64), 0, st, p);
+    hipLaunchKernelGGL(sn_mask_condition_combined_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cp);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_aabb_mask_condition_combined launch: ") + hipGetErrorString(e));
     return SN_OK;
 }
 

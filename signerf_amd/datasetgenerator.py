@@ -10,7 +10,9 @@ small kernels behind ``sn_aabb_mask_condition`` and nothing leaves the device.
 ``masking_mode="shape"`` (:711-754): the proxy mesh of ``DatasetGeneratorConfig.renderer`` (the bunny by default) is rasterised to a
 z-depth image by ``sn_mesh_raster_depth`` (``renderer.Renderer``; the reference draws it with pyrender on OpenGL), and
 ``sn_shape_mask_condition`` builds the mask and the condition from the mesh depth and the NeRF depth -- again without a host round trip.
-``combine_shape_with_depth`` (aabb mode with the mesh's shaded colour) is not built: the flag is carried and has no effect.
+``combine_shape_with_depth`` (:794-811): in aabb mode the same proxy mesh is also rasterised to a shaded colour image
+(``sn_mesh_raster_color``, pyrender's ambient-only shading restated), and ``sn_aabb_mask_condition_combined`` pastes its channel 0 into the
+aabb condition wherever the mesh is in front of the NeRF; the mask is the plain aabb mask.
 """
 
 from __future__ import annotations
@@ -54,7 +56,7 @@ class DatasetGeneratorConfig:
     border_width_between_images: int = 0
     inverse_mask: bool = False
     manual_depth: Optional[Tuple[float, float]] = None
-    combine_shape_with_depth: bool = False   # aabb mode + the mesh's shaded colour: not built, carried for signature parity
+    combine_shape_with_depth: bool = False   # aabb mode: the mesh's shaded colour replaces the condition where the mesh is in front
     renderer: Optional[RendererConfig] = None
 
 
@@ -85,6 +87,43 @@ def aabb_mask_and_condition(depth: Tensor, rays_o: Tensor, rays_d: Tensor, aabb:
         _lib.check(lib.sn_aabb_mask_condition(_lib.ptr(o), _lib.ptr(d), _lib.ptr(z), H, W, box, C.byref(opts), _lib.ptr(mask),
                                               _lib.ptr(cond), ws.data_ptr(), ws.numel(), _lib.current_stream()),
                    None, "sn_aabb_mask_condition")
+    return mask.bool(), cond
+
+
+def aabb_mask_and_condition_combined(depth: Tensor, rays_o: Tensor, rays_d: Tensor, aabb: Tensor, mesh_depth: Tensor, mesh_color: Tensor,
+                                     mask_dialation: Optional[Tuple[int, int]] = (50, 50), inverse_mask: bool = False,
+                                     manual_depth: Optional[Tuple[float, float]] = None, additional_depth_radius: float = 0.1,
+                                     with_condition: bool = True):
+    """datasetgenerator.py:758-818 with ``combine_shape_with_depth`` on the GPU.  As ``aabb_mask_and_condition`` (the same mask, bit for
+    bit), plus mesh_depth [H,W,1] fp32 and mesh_color [H,W,3] uint8 (``Renderer.render_camera(camera, with_color=True)``): where
+    something is visible the condition is 1 - clamp(cv * mesh_color[..., 0] / 255 + !cv * nerf_norm, 0, 1) with
+    cv = (mesh_depth < depth) & (mesh_depth > 0) (:798-811).  If nothing is visible both are all-zero, as in the reference."""
+    lib = _lib.load()
+    H, W = depth.shape[0], depth.shape[1]
+    dev = depth.device
+    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+    o, d, z, md = f32(rays_o), f32(rays_d), f32(depth), f32(mesh_depth)
+    mc = mesh_color.to(device=dev).contiguous()
+    if md.numel() != H * W or mc.dtype != torch.uint8 or tuple(mc.shape) != (H, W, 3):
+        raise ValueError(f"mesh depth {tuple(mesh_depth.shape)} must be [H,W,1] and mesh colour {tuple(mesh_color.shape)} {mesh_color.dtype} "
+                         f"[H,W,3] uint8 for a NeRF depth of {tuple(depth.shape)}")
+    opts = _lib.SnMaskOpts()
+    opts.inverse_mask = int(bool(inverse_mask))
+    if mask_dialation is not None:
+        opts.dilate_w, opts.dilate_h = int(mask_dialation[0]), int(mask_dialation[1])
+    opts.has_manual_depth = int(manual_depth is not None)
+    if manual_depth is not None:
+        opts.manual_min, opts.manual_max = float(manual_depth[0]), float(manual_depth[1])
+    opts.additional_depth_radius = float(additional_depth_radius)
+    box = (C.c_float * 6)(*aabb.detach().to("cpu", torch.float32).reshape(-1).tolist())
+    with torch.cuda.device(dev):
+        mask = torch.empty((H, W, 1), dtype=torch.uint8, device=dev)
+        cond = torch.empty((H, W, 1), dtype=torch.float32, device=dev) if with_condition else None
+        ws = torch.empty(lib.sn_mask_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
+        _lib.check(lib.sn_aabb_mask_condition_combined(_lib.ptr(o), _lib.ptr(d), _lib.ptr(z), H, W, box, C.byref(opts), _lib.ptr(md),
+                                                       _lib.ptr(mc), _lib.ptr(mask), _lib.ptr(cond), ws.data_ptr(), ws.numel(),
+                                                       _lib.current_stream()),
+                   None, "sn_aabb_mask_condition_combined")
     return mask.bool(), cond
 
 
@@ -119,10 +158,14 @@ def shape_mask_and_condition(mesh_depth: Tensor, depth: Tensor, mask_dialation: 
 
 
 def render_camera(config: DatasetGeneratorConfig, graph, camera, with_mask: bool = True, with_condition: bool = True,
-                  renderer: Optional[Renderer] = None):
+                  renderer: Optional[Renderer] = None, combine_shape_with_depth: Optional[bool] = None):
     """One camera: rgb, mask, condition (datasetgenerator.py:677-820).  `camera`: a 0-dim ``Cameras`` of this package or any object with
     nerfstudio's camera accessors (adopted: ray generation always runs in the HIP kernel).  ``masking_mode="shape"`` needs `renderer`
-    (a ``renderer.Renderer`` after ``setup()``), as the reference needs ``self.renderer``."""
+    (a ``renderer.Renderer`` after ``setup()``), as the reference needs ``self.renderer``.
+
+    ``combine_shape_with_depth`` (None: ``config.combine_shape_with_depth``) applies to the aabb mode's condition and needs `renderer` too.
+    Without one it raises the reference's ValueError whenever a condition is asked for -- the reference raises only once it has found
+    something visible, which here would take a host sync; the shape mode ignores the flag, as in the reference."""
     camera = _adopt(camera)
     camera_ray_bundle = camera.generate_rays(camera_indices=0, aabb_box=graph.render_aabb)
     graph.eval()
@@ -145,6 +188,15 @@ def render_camera(config: DatasetGeneratorConfig, graph, camera, with_mask: bool
     if config.masking_mode != "aabb":
         raise NotImplementedError(f"masking_mode={config.masking_mode!r}: the reference knows 'aabb' and 'shape'")
     aabb = torch.tensor([config.aabb_min, config.aabb_max], dtype=torch.float32)
+    combine = config.combine_shape_with_depth if combine_shape_with_depth is None else combine_shape_with_depth
+    if combine and with_condition:
+        if renderer is None:
+            raise ValueError("Renderer is None but masking mode is shape")   # (the reference's message, :796)
+        mesh_color, mesh_depth = renderer.render_camera(camera, with_color=True)
+        mask, cond = aabb_mask_and_condition_combined(depth, camera_ray_bundle.origins, camera_ray_bundle.directions, aabb, mesh_depth,
+                                                      mesh_color, config.mask_dialation, config.inverse_mask, config.manual_depth,
+                                                      config.additional_depth_radius)
+        return rgb, mask, cond
     mask, cond = aabb_mask_and_condition(depth, camera_ray_bundle.origins, camera_ray_bundle.directions, aabb, config.mask_dialation,
                                          config.inverse_mask, config.manual_depth, config.additional_depth_radius, with_condition)
     if not with_condition:
@@ -336,8 +388,10 @@ class DatasetGenerator:
         self.rows, self.cols = config.rows, config.cols
         self.border_width_between_images = config.border_width_between_images
         self.mask_dialation, self.additional_depth_radius, self.manual_depth = config.mask_dialation, config.additional_depth_radius, config.manual_depth
-        # the proxy mesh of the shape mode; set up (mesh parsed) at the start of generate_dataset, as the reference does at :226
-        self.renderer = Renderer(config.renderer or RendererConfig(), device=device) if self.masking_mode == "shape" else None
+        # the proxy mesh of the shape mode and of the aabb mode with combine_shape_with_depth; set up (mesh parsed) at the start of
+        # generate_dataset, as the reference does at :226
+        uses_mesh = self.masking_mode == "shape" or (self.masking_mode == "aabb" and bool(self.combine_shape_with_depth))
+        self.renderer = Renderer(config.renderer or RendererConfig(), device=device) if uses_mesh else None
         self.diffuse = diffuse or identity_diffuse
         self.group = group
         if save_workers is None:  # PNG encoding is the slowest stage of the loop: spread it over the host's cores (dataset_io.encode_png releases the GIL)
@@ -413,18 +467,24 @@ class DatasetGenerator:
             self.renderer.setup()
         return self.renderer
 
-    def _render_module_fn(self, config, graph, camera, with_mask: bool = True, with_condition: bool = True):
-        # the module-level render_camera, looked up at call time; `renderer` is only passed in shape mode, so an aabb run calls it exactly
-        # as before
+    def _render_module_fn(self, config, graph, camera, with_mask: bool = True, with_condition: bool = True,
+                          combine_shape_with_depth: Optional[bool] = None):
+        # the module-level render_camera, looked up at call time; `renderer` is only passed when there is a mesh (shape mode, or aabb mode
+        # with combine_shape_with_depth), so a plain aabb run calls it exactly as before.  combine_shape_with_depth None: the config's
+        # flag, which the pre-computed views (precompute_views) are rendered with.
+        kw = {} if combine_shape_with_depth is None else {"combine_shape_with_depth": combine_shape_with_depth}
         if self.renderer is None:
-            return render_camera(config, graph, camera, with_mask, with_condition)
-        return render_camera(config, graph, camera, with_mask, with_condition, renderer=self._ready_renderer())
+            return render_camera(config, graph, camera, with_mask, with_condition, **kw)
+        return render_camera(config, graph, camera, with_mask, with_condition, renderer=self._ready_renderer(), **kw)
 
     def render_camera(self, graph, camera, with_mask: bool = True, with_condition: bool = True, combine_shape_with_depth: bool = False):
-        """datasetgenerator.py:677-820: a pre-computed view when there is one, else rendered now."""
-        hit = self._views.get(_camera_key(camera)) if (with_mask and with_condition) else None
+        """datasetgenerator.py:677-820: a pre-computed view when there is one (and it was rendered with the same
+        ``combine_shape_with_depth``), else rendered now."""
+        same_flag = bool(combine_shape_with_depth) == bool(self.config.combine_shape_with_depth)
+        hit = self._views.get(_camera_key(camera)) if (with_mask and with_condition and (same_flag or self.masking_mode != "aabb")) else None
         if hit is None:
-            return self._render_module_fn(self.config, graph, camera, with_mask, with_condition)
+            return self._render_module_fn(self.config, graph, camera, with_mask, with_condition,
+                                          None if same_flag else bool(combine_shape_with_depth))
         tiles, i = hit
         return tiles[i, :, :, 0:3].contiguous(), tiles[i, :, :, 3:4] > 0.5, tiles[i, :, :, 4:5].contiguous()
 

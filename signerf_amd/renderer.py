@@ -1,10 +1,11 @@
-"""The proxy-mesh depth renderer of ``masking_mode="shape"`` (/root/reference/signerf/renderer/renderer.py).
+"""The proxy-mesh renderer of ``masking_mode="shape"`` and of ``combine_shape_with_depth`` (/root/reference/signerf/renderer/renderer.py).
 
 The reference loads the mesh with trimesh, places it with ``pose = [R . S | position]`` and renders it with pyrender on OpenGL / EGL,
 one offscreen renderer and one host read-back per view.  Here the mesh is parsed once (``load_obj``), uploaded once per device
 (``Renderer.setup``), and every view is one call of ``sn_mesh_raster_depth``: a z-depth image on the GPU, sampled at the NeRF's pixel
-centres (DESIGN.md "Shape masking mode" lists what differs from pyrender's multisampled 24-bit depth buffer).  The colour image is not
-produced: ``render_camera`` returns ``(None, depth)``.
+centres (DESIGN.md "Shape masking mode" lists what differs from pyrender's multisampled 24-bit depth buffer).  ``render_camera`` returns
+``(None, depth)``; with ``with_color=True`` it returns ``(color, depth)`` from one call of ``sn_mesh_raster_color``, the colour shaded as
+pyrender shades a mesh under the reference's ambient-only light (``shade_defaults``; the constants are UNPINNED).
 """
 
 from __future__ import annotations
@@ -34,16 +35,21 @@ class RendererConfig:
     """degrees about x, y, z; applied as Rz . Ry . Rx"""
     scale: List[float] = field(default_factory=lambda: [0.1, 0.1, 0.1])
     color: List[float] = field(default_factory=lambda: [0.0, 0.0, 0.0, 1.0])
-    """carried for config parity: the colour image is not rendered"""
+    """carried for config parity and not applied, as in the reference (which stores it and never uses it): the colour image is shaded
+    with the mesh's own material (``shade_defaults``)"""
     object_path: str = field(default_factory=lambda: "models/bunny.obj")
     cull_back_faces: bool = True
     """pyrender draws a mesh without a double-sided material with GL_BACK culling; False draws both sides"""
 
 
-def load_obj(path) -> Tuple[np.ndarray, np.ndarray]:
+def load_obj(path, with_colors: bool = False):
     """Wavefront OBJ -> (vertices [V,3] float32, triangles [F,3] int32).  ``v x y z [r g b]``; ``f`` with ``a``, ``a/b``, ``a//c`` or
     ``a/b/c`` corners, 1-based or negative (relative) indices, polygons split into triangle fans.  ``vt vn vp o g s l usemtl mtllib`` and
-    comments are ignored.  Raises ``ValueError`` / ``FileNotFoundError`` with the file and line for anything else."""
+    comments are ignored.  Raises ``ValueError`` / ``FileNotFoundError`` with the file and line for anything else.
+
+    ``with_colors=True``: -> (vertices, triangles, colors), colors [V,4] uint8 RGBA (alpha 255) from ``v x y z r g b``, or None when no
+    vertex carries a colour.  Colours within [0, 1] are quantised as ``np.round(c * 255)``; a file with any component above 1 is read as
+    0..255 values.  A file where only some vertices carry a colour raises ``ValueError`` with the file and line."""
     p = Path(path)
     if p.suffix.lower() != ".obj":
         raise ValueError(f"{p}: not an .obj file (the shape masking mode reads Wavefront OBJ meshes only)")
@@ -51,6 +57,8 @@ def load_obj(path) -> Tuple[np.ndarray, np.ndarray]:
         raise FileNotFoundError(f"{p}: mesh file not found")
     verts: List[Tuple[float, float, float]] = []
     tris: List[Tuple[int, int, int]] = []
+    colors: List[Tuple[float, float, float]] = []
+    first_v: Optional[Tuple[int, bool]] = None   # (line, has a colour) of the first vertex
     with open(p, "r", encoding="utf8", errors="replace") as fh:
         for ln, line in enumerate(fh, 1):
             parts = line.split("#", 1)[0].split()
@@ -64,6 +72,18 @@ def load_obj(path) -> Tuple[np.ndarray, np.ndarray]:
                     verts.append((float(parts[1]), float(parts[2]), float(parts[3])))
                 except ValueError as e:
                     raise ValueError(f"{p}:{ln}: bad vertex: {e}") from None
+                if with_colors:
+                    has = len(parts) == 7
+                    if first_v is None:
+                        first_v = (ln, has)
+                    elif has != first_v[1]:
+                        raise ValueError(f"{p}:{ln}: this vertex {'has' if has else 'has no'} colour but the first one (line {first_v[0]}) "
+                                         f"{'has' if first_v[1] else 'has none'}: either every vertex carries r g b or none does")
+                    if has:
+                        try:
+                            colors.append((float(parts[4]), float(parts[5]), float(parts[6])))
+                        except ValueError as e:
+                            raise ValueError(f"{p}:{ln}: bad vertex colour: {e}") from None
             elif key == "f":
                 if len(parts) < 4:
                     raise ValueError(f"{p}:{ln}: a face needs at least three corners")
@@ -87,7 +107,19 @@ def load_obj(path) -> Tuple[np.ndarray, np.ndarray]:
             # vt, vn, vp, o, g, s, l, usemtl, mtllib, ...: not geometry this renderer draws
     if not tris:
         raise ValueError(f"{p}: no faces")
-    return np.asarray(verts, dtype=np.float32).reshape(-1, 3), np.asarray(tris, dtype=np.int32).reshape(-1, 3)
+    v, f = np.asarray(verts, dtype=np.float32).reshape(-1, 3), np.asarray(tris, dtype=np.int32).reshape(-1, 3)
+    if not with_colors:
+        return v, f
+    if not colors:
+        return v, f, None
+    c = np.asarray(colors, dtype=np.float64)
+    if not np.isfinite(c).all() or (c < 0).any() or (c > 255).any():
+        raise ValueError(f"{p}: vertex colours must lie in [0, 1] (or 0..255)")
+    if (c <= 1.0).all():
+        c = c * 255.0
+    rgba = np.full((c.shape[0], 4), 255, dtype=np.uint8)
+    rgba[:, :3] = np.round(c).astype(np.uint8)
+    return v, f, rgba
 
 
 def object_pose(cfg: RendererConfig) -> np.ndarray:
@@ -132,8 +164,57 @@ def raster_depth(vertices: Tensor, triangles: Tensor, mv, fx: float, fy: float, 
     return depth
 
 
+# pyrender's mesh shader under the reference's Scene(ambient_light=[1, 1, 1]) with no other light, as recalled from pyrender 0.1.45 --
+# UNPINNED (pyrender is not available to check against; tools/make_pyrender_fixture.py writes the fixtures that pin them):
+#   linear = ambient * baseColorFactor.rgb * COLOR_0, out = clamp(pow(linear, 1 / 2.2), 0, 1) -> unorm8, the clear colour elsewhere.
+PYRENDER_DEFAULT_BASE_COLOR = (0.3, 0.3, 0.3, 1.0)   # the default material of a trimesh without visuals (the bunny: no bunny1.mtl)
+PYRENDER_VERTEX_COLOR_BASE_COLOR = (1.0, 1.0, 1.0, 1.0)   # the material of a mesh with vertex colours
+PYRENDER_BACKGROUND = (1.0, 1.0, 1.0)   # Scene's default bg_color (white)
+REFERENCE_AMBIENT = (1.0, 1.0, 1.0)     # renderer.py:130
+
+
+def shade_defaults(has_vertex_colors: bool) -> Dict[str, object]:
+    """The ``raster_color`` shading keywords that stand for pyrender's, for a mesh with or without vertex colours (UNPINNED)."""
+    return {"base_color": PYRENDER_VERTEX_COLOR_BASE_COLOR if has_vertex_colors else PYRENDER_DEFAULT_BASE_COLOR,
+            "ambient": REFERENCE_AMBIENT, "background": PYRENDER_BACKGROUND, "gamma": True}
+
+
+def raster_color(vertices: Tensor, triangles: Tensor, mv, fx: float, fy: float, cx: float, cy: float, height: int, width: int,
+                 vertex_colors: Optional[Tensor] = None, base_color=PYRENDER_DEFAULT_BASE_COLOR, ambient=REFERENCE_AMBIENT,
+                 background=PYRENDER_BACKGROUND, gamma: bool = True, znear: float = ZNEAR, zfar: float = ZFAR, cull_back_faces: bool = True,
+                 with_depth: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
+    """``sn_mesh_raster_color``: as ``raster_depth``, plus vertex_colors [V,4] uint8 RGBA on the GPU (or None) and the shading
+    (``shade_defaults``) -> (color [H,W,3] uint8, depth [H,W,1] fp32 or None) on the GPU.  The depth is bit-identical to
+    ``raster_depth``'s."""
+    lib = _lib.load()
+    dev = vertices.device
+    if vertex_colors is not None and (vertex_colors.dtype != torch.uint8 or tuple(vertex_colors.shape) != (int(vertices.shape[0]), 4)):
+        raise ValueError(f"vertex_colors must be [V,4] uint8 with V = {int(vertices.shape[0])}, got {tuple(vertex_colors.shape)} "
+                         f"{vertex_colors.dtype}")
+    opts = _lib.SnMeshRasterOpts()
+    opts.znear, opts.zfar, opts.cull_back_faces = float(znear), float(zfar), int(bool(cull_back_faces))
+    shade = _lib.SnMeshShadeOpts()
+    shade.base_color[:] = [float(x) for x in base_color]
+    shade.ambient[:] = [float(x) for x in ambient]
+    shade.background[:] = [float(x) for x in background]
+    shade.gamma = int(bool(gamma))
+    m = (C.c_float * 12)(*np.asarray(mv, dtype=np.float64).reshape(12).tolist())
+    F = int(triangles.shape[0])
+    with torch.cuda.device(dev):
+        color = torch.empty((height, width, 3), dtype=torch.uint8, device=dev)
+        depth = torch.empty((height, width, 1), dtype=torch.float32, device=dev) if with_depth else None
+        ws = torch.empty(max(lib.sn_mesh_color_workspace_bytes(F, height, width), 1), dtype=torch.uint8, device=dev)
+        vc = None if vertex_colors is None else vertex_colors.contiguous()
+        _lib.check(lib.sn_mesh_raster_color(_lib.ptr(vertices), int(vertices.shape[0]), _lib.ptr(vc), _lib.ptr(triangles), F, m, float(fx),
+                                            float(fy), float(cx), float(cy), int(height), int(width), C.byref(opts), C.byref(shade),
+                                            _lib.ptr(depth), _lib.ptr(color), ws.data_ptr(), ws.numel(), _lib.current_stream()),
+                   None, "sn_mesh_raster_color")
+    return color, depth
+
+
 class Renderer:
-    """``Renderer`` of the reference (renderer.py:43-196) for the depth it feeds the shape masking mode."""
+    """``Renderer`` of the reference (renderer.py:43-196): the depth it feeds the shape masking mode and the colour + depth that
+    ``combine_shape_with_depth`` pastes into the aabb condition."""
 
     def __init__(self, config: RendererConfig, device="cuda") -> None:
         self.config = config
@@ -142,13 +223,15 @@ class Renderer:
         self.object_path = config.object_path
         self.pose: Optional[np.ndarray] = None
         self._host_mesh: Optional[Tuple[np.ndarray, np.ndarray]] = None
+        self._host_colors: Optional[Tuple[Optional[np.ndarray]]] = None   # ([V,4] uint8 vertex colours or None,) once read
         self._uploaded: Dict[str, Tuple[Tensor, Tensor]] = {}
+        self._uploaded_colors: Dict[str, Optional[Tensor]] = {}
 
     def setup(self) -> None:
         """Parse the mesh and compute its pose (renderer.py:64-121).  Unlike the reference, a missing or non-OBJ file raises here."""
         self._host_mesh = load_obj(self.object_path)
         self.pose = object_pose(self.config)
-        self._uploaded = {}
+        self._host_colors, self._uploaded, self._uploaded_colors = None, {}, {}
 
     @property
     def num_triangles(self) -> int:
@@ -167,8 +250,21 @@ class Renderer:
             self._uploaded[key] = (torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev))
         return self._uploaded[key]
 
-    def render_camera(self, camera) -> Tuple[None, Tensor]:
-        """-> (None, depth [H,W,1] fp32 on the camera's device).  Intrinsics and pose come from the camera's host mirror (no device
+    def colors_on(self, device) -> Optional[Tensor]:
+        """The vertex colours [V,4] uint8 on `device`, or None when the mesh has none.  The file's colours are read the first time a
+        colour image is rendered (so a mesh whose colours are malformed still renders its depth, as before), uploaded once per device."""
+        verts, _ = self.mesh_on(device)
+        if self._host_colors is None:
+            self._host_colors = (load_obj(self.object_path, with_colors=True)[2],)
+        key = str(verts.device)
+        if key not in self._uploaded_colors:
+            c = self._host_colors[0]
+            self._uploaded_colors[key] = None if c is None else torch.from_numpy(c).to(verts.device)
+        return self._uploaded_colors[key]
+
+    def render_camera(self, camera, with_color: bool = False) -> Tuple[Optional[Tensor], Tensor]:
+        """-> (None, depth [H,W,1] fp32 on the camera's device); with_color: (color [H,W,3] uint8, depth), shaded as pyrender shades the
+        mesh under the reference's ambient light (``shade_defaults``).  Intrinsics and pose come from the camera's host mirror (no device
         sync); pinhole only -- distortion and camera type are ignored, as pyrender's IntrinsicsCamera ignores them."""
         from .cameras import Cameras
 
@@ -179,4 +275,8 @@ class Renderer:
         dev = cam.device if cam.device.type == "cuda" else torch.device(self.device)
         verts, tris = self.mesh_on(dev)
         mv = model_view(host[:12], self.pose)
-        return None, raster_depth(verts, tris, mv, fx, fy, cx, cy, H, W, ZNEAR, ZFAR, self.config.cull_back_faces)
+        if not with_color:
+            return None, raster_depth(verts, tris, mv, fx, fy, cx, cy, H, W, ZNEAR, ZFAR, self.config.cull_back_faces)
+        vc = self.colors_on(dev)
+        return raster_color(verts, tris, mv, fx, fy, cx, cy, H, W, vc, znear=ZNEAR, zfar=ZFAR, cull_back_faces=self.config.cull_back_faces,
+                            **shade_defaults(vc is not None))

@@ -10,6 +10,13 @@ Meshes (tests/mesh_oracle.py's procedural icosphere restated here: tools do not 
   big_1.3M      a 1 310 720-face icosphere in the bunny's place
 
     python tools/shape_mask_bench.py [--size 800] [--reps 50] [--json OUT]
+
+--combine times the aabb mode's combine_shape_with_depth instead (bunny_5120 and closeup_5120): the colour raster
+(sn_mesh_raster_color, colour + depth) against the depth raster, and the combined aabb step (sn_aabb_mask_condition_combined) against
+the plain one (sn_aabb_mask_condition); flag_share = what the flag adds to a view (colour raster + combined step - plain step) over the
+NeRF render.
+
+    python tools/shape_mask_bench.py --combine [--size 800] [--reps 50] [--json OUT]
 """
 import argparse
 import json
@@ -22,8 +29,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from signerf_amd import Cameras, scene  # noqa: E402
-from signerf_amd.datasetgenerator import shape_mask_and_condition  # noqa: E402
-from signerf_amd.renderer import RendererConfig, model_view, object_pose, raster_depth  # noqa: E402
+from signerf_amd.datasetgenerator import aabb_mask_and_condition, aabb_mask_and_condition_combined, shape_mask_and_condition  # noqa: E402
+from signerf_amd.renderer import RendererConfig, model_view, object_pose, raster_color, raster_depth  # noqa: E402
 
 
 def icosphere(subdivisions):
@@ -63,6 +70,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--nerf-reps", type=int, default=10)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--combine", action="store_true", help="time combine_shape_with_depth (see the module docstring)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     S = a.size
@@ -73,6 +81,8 @@ def main():
     c2w = scene.benchmark_cameras(8)[:, :3]
     cams = Cameras(c2w, 1.2 * S, 1.2 * S, S / 2, S / 2, S, S).to(dev)
     pose = object_pose(RendererConfig(scale=[0.015, 0.015, 0.015]))   # radius 0.15, about the bunny's extent at the default scale
+    if a.combine:
+        return combine(a, model, cams, pose, dev)
     meshes = {"bunny_5120": icosphere(4), "big_1.3M": icosphere(8)}
     rows = []
     for view in range(0, 8, 2):
@@ -103,6 +113,45 @@ def main():
         summary[name] = {k: float(np.median([r[k] for r in rs])) for k in ("raster_ms", "mask_ms", "raster_plus_mask_ms", "nerf_render_ms",
                                                                              "share_of_render", "mesh_coverage")}
     out = {"size": S, "reps": a.reps, "gpu": torch.cuda.get_device_name(0), "median_over_views": summary, "rows": rows}
+    print(json.dumps({"median_over_views": summary}))
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+
+
+def combine(a, model, cams, pose, dev):
+    S = a.size
+    v, f = icosphere(4)
+    vt, ft = torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev)
+    box = torch.tensor([[-0.1, -0.1, -0.1], [0.1, 0.1, 0.1]])   # DatasetGeneratorConfig's default aabb
+    rows = []
+    for view in range(0, 8, 2):
+        cam = cams[view]
+        bundle = cam.generate_rays(0, aabb_box=model.render_aabb)
+        nerf_ms = timed(lambda: model.get_outputs_for_camera_ray_bundle(bundle), a.nerf_reps, 2)
+        nerf_depth = model.get_outputs_for_camera_ray_bundle(bundle)["depth"]
+        o, d = bundle.origins.contiguous(), bundle.directions.contiguous()
+        host = cam._host[0].tolist()
+        close = model_view(host[:12], pose).copy()
+        close[:, 3] = [0.0, 0.0, -0.27]
+        for name, mv in (("bunny_5120", model_view(host[:12], pose)), ("closeup_5120", close)):
+            intr = (host[12], host[13], host[14], host[15], S, S)
+            d_ms = timed(lambda: raster_depth(vt, ft, mv, *intr), a.reps, a.warmup)
+            c_ms = timed(lambda: raster_color(vt, ft, mv, *intr), a.reps, a.warmup)
+            color, md = raster_color(vt, ft, mv, *intr)
+            p_ms = timed(lambda: aabb_mask_and_condition(nerf_depth, o, d, box), a.reps, a.warmup)
+            k_ms = timed(lambda: aabb_mask_and_condition_combined(nerf_depth, o, d, box, md, color), a.reps, a.warmup)
+            cv = float(((md > 0) & (md < nerf_depth)).float().mean())
+            rows.append({"view": view, "mesh": name, "faces": int(f.shape[0]), "depth_raster_ms": round(d_ms, 4), "color_raster_ms": round(c_ms, 4),
+                         "color_over_depth": round(c_ms / d_ms, 4), "plain_aabb_ms": round(p_ms, 4), "combined_aabb_ms": round(k_ms, 4),
+                         "combined_minus_plain_ms": round(k_ms - p_ms, 4), "nerf_render_ms": round(nerf_ms, 3),
+                         "flag_share": round((c_ms + k_ms - p_ms) / nerf_ms, 4), "mesh_coverage": round(float((md > 0).float().mean()), 4),
+                         "mesh_in_front": round(cv, 4)})
+            print(json.dumps(rows[-1]), flush=True)
+    keys = ("depth_raster_ms", "color_raster_ms", "color_over_depth", "plain_aabb_ms", "combined_aabb_ms", "combined_minus_plain_ms",
+            "nerf_render_ms", "flag_share", "mesh_coverage", "mesh_in_front")
+    summary = {name: {k: float(np.median([r[k] for r in rows if r["mesh"] == name])) for k in keys} for name in ("bunny_5120", "closeup_5120")}
+    out = {"size": S, "reps": a.reps, "gpu": torch.cuda.get_device_name(0), "leg": "combine", "median_over_views": summary, "rows": rows}
     print(json.dumps({"median_over_views": summary}))
     if a.json:
         with open(a.json, "w") as fh:
