@@ -18,7 +18,7 @@ SN_MESH_ABI_VERSION = 1   # include/signerf_hip_mesh.h, checked the same way
 SN_MESH_COLOR_ABI_VERSION = 1   # include/signerf_hip_mesh_color.h, checked the same way
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
-# SIGNERF_HIP_LIB: load another build of the library (A/B experiments with tools/ab_lib.py); the default is the in-tree build
+# SIGNERF_HIP_LIB: load another build of the library (A/B experiments with tools/ab_lib.sh); the default is the in-tree build
 LIB_PATH = os.environ.get("SIGNERF_HIP_LIB") or os.path.join(_PKG_DIR, "libsignerf_hip.so")
 
 

@@ -2278,37 +2278,50 @@ static void fill_mask_params(const SnMaskOpts* opts, const float* depth, int32_t
     p.condition = condition;
 }
 
+// What the three mask entry points share, for the entry point `who`: adopt and validate SnMaskOpts, check the workspace and clear
+// its stamp, fill p (fill_mask_params) and reset the three statistics words on the stream.
+static int begin_mask_step(const std::string& who, const SnMaskOpts* opts, const float* depth, int32_t height, int32_t width, uint8_t* mask,
+                           float* condition, void* workspace, size_t workspace_bytes, hipStream_t st, SnMaskParams& p) {
+    SnMaskOpts o;
+    if (int rc = adopt_struct(nullptr, opts, kMaskOptsMin, o, (who + ": SnMaskOpts").c_str())) return rc;
+    if (o.dilate_w < 0 || o.dilate_h < 0 || o.dilate_w > SN_MASK_MAX_K || o.dilate_h > SN_MASK_MAX_K || ((o.dilate_w == 0) != (o.dilate_h == 0)))
+        return fail(nullptr, SN_ERR_INVALID, who + ": dilation size must be 0 or within [1," + std::to_string(SN_MASK_MAX_K) + "] in both dimensions");
+    if (!workspace || workspace_bytes < sn_mask_workspace_bytes(height, width)) return fail(nullptr, SN_ERR_WORKSPACE, who + ": workspace too small");
+    clear_stamp(workspace);  // (a caller may hand the mask step the memory a render used: its bins are gone then)
+    fill_mask_params(&o, depth, height, width, workspace, mask, condition, p);
+    hipError_t e = hipMemsetAsync(p.stats, 0, 4, st);                    // count
+    if (e == hipSuccess) e = hipMemsetAsync(p.stats + 1, 0xff, 4, st);  // ordered min
+    if (e == hipSuccess) e = hipMemsetAsync(p.stats + 2, 0, 4, st);     // ordered max
+    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, who + " memset: " + hipGetErrorString(e));
+    return SN_OK;
+}
+
+static int end_launches(const std::string& who) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, who + " launch: " + hipGetErrorString(e));
+    return SN_OK;
+}
+
+static dim3 mask_visible_grid(size_t n) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, SN_MASK_VIS_BLOCKS)); }
+static dim3 per_pixel_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
 int sn_aabb_mask_condition(const float* origins, const float* directions, const float* depth, int32_t height, int32_t width,
                            const float* aabb, const SnMaskOpts* opts, uint8_t* mask, float* condition, void* workspace,
                            size_t workspace_bytes, SnStream stream) {
+    const std::string who = "sn_aabb_mask_condition";
     if (!origins || !directions || !depth || !aabb || !opts || !mask || height <= 0 || width <= 0)
-        return fail(nullptr, SN_ERR_INVALID, "sn_aabb_mask_condition: bad argument");
-    SnMaskOpts opts_own;
-    if (int rc = adopt_struct(nullptr, opts, kMaskOptsMin, opts_own, "sn_aabb_mask_condition: SnMaskOpts")) return rc;
-    opts = &opts_own;
-    if (opts->dilate_w < 0 || opts->dilate_h < 0 || opts->dilate_w > SN_MASK_MAX_K || opts->dilate_h > SN_MASK_MAX_K ||
-        ((opts->dilate_w == 0) != (opts->dilate_h == 0)))
-        return fail(nullptr, SN_ERR_INVALID, "sn_aabb_mask_condition: dilation size must be 0 or within [1," + std::to_string(SN_MASK_MAX_K) + "] in both dimensions");
-    if (!workspace || workspace_bytes < sn_mask_workspace_bytes(height, width))
-        return fail(nullptr, SN_ERR_WORKSPACE, "sn_aabb_mask_condition: workspace too small");
-    clear_stamp(workspace);  // (a caller may hand the mask step the memory a render used: its bins are gone then)
+        return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)height * width;
     SnMaskParams p;
-    fill_mask_params(opts, depth, height, width, workspace, mask, condition, p);
+    if (int rc = begin_mask_step(who, opts, depth, height, width, mask, condition, workspace, workspace_bytes, st, p)) return rc;
     p.origins = origins;
     p.directions = directions;
     memcpy(p.aabb, aabb, sizeof(p.aabb));
-    hipError_t e = hipMemsetAsync(p.stats, 0, 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(p.stats + 1, 0xff, 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(p.stats + 2, 0, 4, st);
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_aabb_mask_condition memset: ") + hipGetErrorString(e));
-    hipLaunchKernelGGL(sn_mask_visible_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, SN_MASK_VIS_BLOCKS)), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(sn_mask_visible_kernel, mask_visible_grid(n), dim3(256), 0, st, p);
     if (p.dilate) hipLaunchKernelGGL(sn_mask_prefix_kernel, dim3((unsigned)height), dim3(64), 0, st, p);
-    hipLaunchKernelGGL(sn_mask_condition_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_aabb_mask_condition launch: ") + hipGetErrorString(e));
-    return SN_OK;
+    hipLaunchKernelGGL(sn_mask_condition_kernel, per_pixel_grid(n), dim3(256), 0, st, p);
+    return end_launches(who);
 }
 
 
@@ -2326,23 +2339,22 @@ size_t sn_mesh_workspace_bytes(int64_t n_triangles, int32_t height, int32_t widt
     return align256(f * sizeof(SnMeshTri)) + align256(f * sizeof(uint2)) + 256;
 }
 
-int sn_mesh_raster_depth(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, const float* model_view,
-                         float fx, float fy, float cx, float cy, int32_t height, int32_t width, const SnMeshRasterOpts* opts, float* depth,
-                         void* workspace, size_t workspace_bytes, SnStream stream) {
-    if (!model_view || !opts || !depth || n_vertices < 0 || n_triangles < 0 || n_triangles > SN_MESH_MAX_TRIS || height <= 0 || width <= 0 ||
+// What the two rasters share, for the entry point `who`: the checks of the mesh, the camera, SnMeshRasterOpts and the workspace (whose
+// stamp is cleared), and the SnMeshRasterParams.  `outputs_ok`: the entry point's own required pointers are there.
+static int begin_raster(const std::string& who, bool outputs_ok, const float* vertices, int64_t n_vertices, const int32_t* triangles,
+                        int64_t n_triangles, const float* model_view, float fx, float fy, float cx, float cy, int32_t height, int32_t width,
+                        const SnMeshRasterOpts* opts, float* depth, void* workspace, size_t workspace_bytes, SnMeshRasterParams& p) {
+    if (!outputs_ok || !model_view || !opts || n_vertices < 0 || n_triangles < 0 || n_triangles > SN_MESH_MAX_TRIS || height <= 0 || width <= 0 ||
         height > SN_MESH_MAX_DIM || width > SN_MESH_MAX_DIM || (n_triangles > 0 && (!vertices || !triangles || n_vertices == 0)))
-        return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_depth: bad argument");
+        return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
     SnMeshRasterOpts o;
-    if (int rc = adopt_struct(nullptr, opts, kMeshRasterOptsMin, o, "sn_mesh_raster_depth: SnMeshRasterOpts")) return rc;
-    if (!(o.znear > 0.0f) || !(o.zfar > o.znear) || !std::isfinite(o.zfar))
-        return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_depth: need 0 < znear < zfar < inf");
+    if (int rc = adopt_struct(nullptr, opts, kMeshRasterOptsMin, o, (who + ": SnMeshRasterOpts").c_str())) return rc;
+    if (!(o.znear > 0.0f) || !(o.zfar > o.znear) || !std::isfinite(o.zfar)) return fail(nullptr, SN_ERR_INVALID, who + ": need 0 < znear < zfar < inf");
     if (!(fx != 0.0f) || !(fy != 0.0f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
-        return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_depth: intrinsics must be finite with fx, fy != 0");
+        return fail(nullptr, SN_ERR_INVALID, who + ": intrinsics must be finite with fx, fy != 0");
     if (!workspace || workspace_bytes < sn_mesh_workspace_bytes(n_triangles, height, width))
-        return fail(nullptr, SN_ERR_WORKSPACE, "sn_mesh_raster_depth: workspace too small");
+        return fail(nullptr, SN_ERR_WORKSPACE, who + ": workspace too small");
     clear_stamp(workspace);
-    hipStream_t st = (hipStream_t)stream;
-    SnMeshRasterParams p;
     memset(&p, 0, sizeof(p));
     p.vertices = vertices;
     p.tris = triangles;
@@ -2362,42 +2374,42 @@ int sn_mesh_raster_depth(const float* vertices, int64_t n_vertices, const int32_
     p.rec = (SnMeshTri*)ws;
     p.bbox = (uint2*)(ws + align256((size_t)n_triangles * sizeof(SnMeshTri)));
     p.depth = depth;
-    if (n_triangles > 0) hipLaunchKernelGGL(sn_mesh_setup_kernel, dim3((unsigned)((n_triangles + 255) / 256)), dim3(256), 0, st, p);
-    hipLaunchKernelGGL(sn_mesh_tile_kernel, dim3((unsigned)((width + SN_MESH_TILE - 1) / SN_MESH_TILE), (unsigned)((height + SN_MESH_TILE - 1) / SN_MESH_TILE)),
-                       dim3(SN_MESH_BATCH), 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_mesh_raster_depth launch: ") + hipGetErrorString(e));
     return SN_OK;
+}
+
+// M-a over the triangles; returns the grid of the tile kernel (M-b or M-e) that follows it
+static dim3 launch_mesh_setup(const SnMeshRasterParams& p, hipStream_t st) {
+    if (p.n_tris > 0) hipLaunchKernelGGL(sn_mesh_setup_kernel, dim3((unsigned)((p.n_tris + 255) / 256)), dim3(256), 0, st, p);
+    return dim3((unsigned)((p.width + SN_MESH_TILE - 1) / SN_MESH_TILE), (unsigned)((p.height + SN_MESH_TILE - 1) / SN_MESH_TILE));
+}
+
+int sn_mesh_raster_depth(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, const float* model_view,
+                         float fx, float fy, float cx, float cy, int32_t height, int32_t width, const SnMeshRasterOpts* opts, float* depth,
+                         void* workspace, size_t workspace_bytes, SnStream stream) {
+    const std::string who = "sn_mesh_raster_depth";
+    SnMeshRasterParams p;
+    if (int rc = begin_raster(who, depth != nullptr, vertices, n_vertices, triangles, n_triangles, model_view, fx, fy, cx, cy, height, width, opts,
+                              depth, workspace, workspace_bytes, p))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(sn_mesh_tile_kernel, launch_mesh_setup(p, st), dim3(SN_MESH_BATCH), 0, st, p);
+    return end_launches(who);
 }
 
 int sn_shape_mask_condition(const float* mesh_depth, const float* nerf_depth, int32_t height, int32_t width, const SnMaskOpts* opts,
                             uint8_t* mask, float* condition, void* workspace, size_t workspace_bytes, SnStream stream) {
+    const std::string who = "sn_shape_mask_condition";
     if (!mesh_depth || !nerf_depth || !opts || !mask || height <= 0 || width <= 0)
-        return fail(nullptr, SN_ERR_INVALID, "sn_shape_mask_condition: bad argument");
-    SnMaskOpts opts_own;
-    if (int rc = adopt_struct(nullptr, opts, kMaskOptsMin, opts_own, "sn_shape_mask_condition: SnMaskOpts")) return rc;
-    opts = &opts_own;
-    if (opts->dilate_w < 0 || opts->dilate_h < 0 || opts->dilate_w > SN_MASK_MAX_K || opts->dilate_h > SN_MASK_MAX_K ||
-        ((opts->dilate_w == 0) != (opts->dilate_h == 0)))
-        return fail(nullptr, SN_ERR_INVALID, "sn_shape_mask_condition: dilation size must be 0 or within [1," + std::to_string(SN_MASK_MAX_K) + "] in both dimensions");
-    if (!workspace || workspace_bytes < sn_mask_workspace_bytes(height, width))
-        return fail(nullptr, SN_ERR_WORKSPACE, "sn_shape_mask_condition: workspace too small");
-    clear_stamp(workspace);
+        return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)height * width;
     SnShapeMaskParams sp;
-    fill_mask_params(opts, nerf_depth, height, width, workspace, mask, condition, sp.m);
+    if (int rc = begin_mask_step(who, opts, nerf_depth, height, width, mask, condition, workspace, workspace_bytes, st, sp.m)) return rc;
     sp.mesh_depth = mesh_depth;
-    hipError_t e = hipMemsetAsync(sp.m.stats, 0, 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(sp.m.stats + 1, 0xff, 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(sp.m.stats + 2, 0, 4, st);
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_shape_mask_condition memset: ") + hipGetErrorString(e));
-    hipLaunchKernelGGL(sn_shape_visible_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, SN_MASK_VIS_BLOCKS)), dim3(256), 0, st, sp);
+    hipLaunchKernelGGL(sn_shape_visible_kernel, mask_visible_grid(n), dim3(256), 0, st, sp);
     if (sp.m.dilate) hipLaunchKernelGGL(sn_mask_prefix_kernel, dim3((unsigned)height), dim3(64), 0, st, sp.m);
-    hipLaunchKernelGGL(sn_shape_condition_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, sp);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_shape_mask_condition launch: ") + hipGetErrorString(e));
-    return SN_OK;
+    hipLaunchKernelGGL(sn_shape_condition_kernel, per_pixel_grid(n), dim3(256), 0, st, sp);
+    return end_launches(who);
 }
 
 
@@ -2414,45 +2426,17 @@ int sn_mesh_raster_color(const float* vertices, int64_t n_vertices, const uint8_
                          int64_t n_triangles, const float* model_view, float fx, float fy, float cx, float cy, int32_t height, int32_t width,
                          const SnMeshRasterOpts* opts, const SnMeshShadeOpts* shade, float* depth, uint8_t* color, void* workspace,
                          size_t workspace_bytes, SnStream stream) {
-    if (!model_view || !opts || !shade || !color || n_vertices < 0 || n_triangles < 0 || n_triangles > SN_MESH_MAX_TRIS || height <= 0 ||
-        width <= 0 || height > SN_MESH_MAX_DIM || width > SN_MESH_MAX_DIM || (n_triangles > 0 && (!vertices || !triangles || n_vertices == 0)))
-        return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_color: bad argument");
-    SnMeshRasterOpts o;
-    if (int rc = adopt_struct(nullptr, opts, kMeshRasterOptsMin, o, "sn_mesh_raster_color: SnMeshRasterOpts")) return rc;
+    const std::string who = "sn_mesh_raster_color";
+    SnMeshColorParams cp;
+    memset(&cp, 0, sizeof(cp));
+    if (int rc = begin_raster(who, shade && color, vertices, n_vertices, triangles, n_triangles, model_view, fx, fy, cx, cy, height, width, opts,
+                              depth, workspace, workspace_bytes, cp.r))
+        return rc;
     SnMeshShadeOpts so;
     if (int rc = adopt_struct(nullptr, shade, kMeshShadeOptsMin, so, "sn_mesh_raster_color: SnMeshShadeOpts")) return rc;
-    if (!(o.znear > 0.0f) || !(o.zfar > o.znear) || !std::isfinite(o.zfar))
-        return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_color: need 0 < znear < zfar < inf");
-    if (!(fx != 0.0f) || !(fy != 0.0f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
-        return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_color: intrinsics must be finite with fx, fy != 0");
     for (int c = 0; c < 3; ++c)
         if (!std::isfinite(so.base_color[c]) || !std::isfinite(so.ambient[c]) || !std::isfinite(so.background[c]))
             return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_color: base_color, ambient and background must be finite");
-    if (!workspace || workspace_bytes < sn_mesh_color_workspace_bytes(n_triangles, height, width))
-        return fail(nullptr, SN_ERR_WORKSPACE, "sn_mesh_raster_color: workspace too small");
-    clear_stamp(workspace);
-    hipStream_t st = (hipStream_t)stream;
-    SnMeshColorParams cp;
-    memset(&cp, 0, sizeof(cp));
-    SnMeshRasterParams& p = cp.r;  // filled as sn_mesh_raster_depth fills it
-    p.vertices = vertices;
-    p.tris = triangles;
-    p.n_vertices = n_vertices;
-    p.n_tris = (int32_t)n_triangles;
-    memcpy(p.mv, model_view, sizeof(p.mv));
-    p.fx = fx;
-    p.fy = fy;
-    p.cx = cx;
-    p.cy = cy;
-    p.height = height;
-    p.width = width;
-    p.znear = o.znear;
-    p.zfar = o.zfar;
-    p.cull = o.cull_back_faces != 0;
-    char* ws = (char*)workspace;
-    p.rec = (SnMeshTri*)ws;
-    p.bbox = (uint2*)(ws + align256((size_t)n_triangles * sizeof(SnMeshTri)));
-    p.depth = depth;
     cp.vertex_colors = vertex_colors;
     for (int c = 0; c < 3; ++c) {
         cp.base[c] = so.base_color[c];
@@ -2461,48 +2445,31 @@ int sn_mesh_raster_color(const float* vertices, int64_t n_vertices, const uint8_
     }
     cp.gamma = so.gamma != 0;
     cp.color = color;
-    if (n_triangles > 0) hipLaunchKernelGGL(sn_mesh_setup_kernel, dim3((unsigned)((n_triangles + 255) / 256)), dim3(256), 0, st, p);
-    hipLaunchKernelGGL(sn_mesh_tile_color_kernel, dim3((unsigned)((width + SN_MESH_TILE - 1) / SN_MESH_TILE), (unsigned)((height + SN_MESH_TILE - 1) / SN_MESH_TILE)),
-                       dim3(SN_MESH_BATCH), 0, st, cp);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_mesh_raster_color launch: ") + hipGetErrorString(e));
-    return SN_OK;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(sn_mesh_tile_color_kernel, launch_mesh_setup(cp.r, st), dim3(SN_MESH_BATCH), 0, st, cp);
+    return end_launches(who);
 }
 
 int sn_aabb_mask_condition_combined(const float* origins, const float* directions, const float* depth, int32_t height, int32_t width,
                                     const float* aabb, const SnMaskOpts* opts, const float* mesh_depth, const uint8_t* mesh_color,
                                     uint8_t* mask, float* condition, void* workspace, size_t workspace_bytes, SnStream stream) {
+    const std::string who = "sn_aabb_mask_condition_combined";
     if (!origins || !directions || !depth || !aabb || !opts || !mesh_depth || !mesh_color || !mask || height <= 0 || width <= 0)
-        return fail(nullptr, SN_ERR_INVALID, "sn_aabb_mask_condition_combined: bad argument");
-    SnMaskOpts opts_own;
-    if (int rc = adopt_struct(nullptr, opts, kMaskOptsMin, opts_own, "sn_aabb_mask_condition_combined: SnMaskOpts")) return rc;
-    opts = &opts_own;
-    if (opts->dilate_w < 0 || opts->dilate_h < 0 || opts->dilate_w > SN_MASK_MAX_K || opts->dilate_h > SN_MASK_MAX_K ||
-        ((opts->dilate_w == 0) != (opts->dilate_h == 0)))
-        return fail(nullptr, SN_ERR_INVALID, "sn_aabb_mask_condition_combined: dilation size must be 0 or within [1," + std::to_string(SN_MASK_MAX_K) + "] in both dimensions");
-    if (!workspace || workspace_bytes < sn_mask_workspace_bytes(height, width))
-        return fail(nullptr, SN_ERR_WORKSPACE, "sn_aabb_mask_condition_combined: workspace too small");
-    clear_stamp(workspace);
+        return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
     hipStream_t st = (hipStream_t)stream;
     const size_t n = (size_t)height * width;
     SnCombinedMaskParams cp;
-    fill_mask_params(opts, depth, height, width, workspace, mask, condition, cp.m);
     SnMaskParams& p = cp.m;
+    if (int rc = begin_mask_step(who, opts, depth, height, width, mask, condition, workspace, workspace_bytes, st, p)) return rc;
     p.origins = origins;
     p.directions = directions;
     memcpy(p.aabb, aabb, sizeof(p.aabb));
     cp.mesh_depth = mesh_depth;
     cp.mesh_color = mesh_color;
-    hipError_t e = hipMemsetAsync(p.stats, 0, 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(p.stats + 1, 0xff, 4, st);
-    if (e == hipSuccess) e = hipMemsetAsync(p.stats + 2, 0, 4, st);
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_aabb_mask_condition_combined memset: ") + hipGetErrorString(e));
-    hipLaunchKernelGGL(sn_mask_visible_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, SN_MASK_VIS_BLOCKS)), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(sn_mask_visible_kernel, mask_visible_grid(n), dim3(256), 0, st, p);
     if (p.dilate) hipLaunchKernelGGL(sn_mask_prefix_kernel, dim3((unsigned)height), dim3(64), 0, st, p);
-    hipLaunchKernelGGL(sn_mask_condition_combined_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, cp);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_aabb_mask_condition_combined launch: ") + hipGetErrorString(e));
-    return SN_OK;
+    hipLaunchKernelGGL(sn_mask_condition_combined_kernel, per_pixel_grid(n), dim3(256), 0, st, cp);
+    return end_launches(who);
 }
 
 

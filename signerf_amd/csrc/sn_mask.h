@@ -1,10 +1,13 @@
 // sn_mask.h -- SURVEY.md §8(f) row 1: the step right after the render on every camera, "aabb" masking mode
-// (/root/reference/signerf/datasetgenerator/datasetgenerator.py:758-818).  The reference round-trips the mask through the
+// (signerf/datasetgenerator/datasetgenerator.py:758-818 of the reference).  The reference round-trips the mask through the
 // CPU for cv2.dilate (:776-778) and syncs on `torch.sum(visible_mask) > 1e-6` (:770); here everything stays on the device:
 //   K-a  slab test (intersection.py:5-56) + visibility mask + count / masked-depth min,max (atomics)
 //   K-b  per-row prefix counts of the mask
 //   K-c  elliptical dilation as "any set pixel in a per-row run" (2 prefix lookups per structuring-element row) fused with
 //        the condition image 1 - clamp((depth - dmin) / (dmax - dmin)), and the "nothing visible -> zeros" branch.
+// The pieces every masking mode's kernels are built from (the shape mode of sn_mesh.h, combine_shape_with_depth of sn_mesh_color.h)
+// are the SN_DEV helpers below: sn_mask_block_reduce (the tail of a visible kernel), sn_mask_nothing_visible, sn_mask_dilated,
+// sn_mask_depth_norm and sn_mask_one_minus_clamp (a condition kernel = these four around its own blend).
 #pragma once
 #include "sn_device.h"
 
@@ -34,13 +37,36 @@ struct SnMaskParams {
     float* condition;  // [H*W] out
 };
 
+// (count, ordered min, ordered max) of a 256-thread workgroup, reduced into thread 0's arguments (wave shuffles, then 4 partials through
+// LDS); the other threads are left with partial values.  Integer sum / min / max: order-independent.
+SN_DEV void sn_mask_block_reduce(uint32_t& cnt, uint32_t& lo, uint32_t& hi) {
+    __shared__ uint32_t red[3][4];
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        cnt += (uint32_t)__shfl_xor((int)cnt, s);
+        lo = min(lo, (uint32_t)__shfl_xor((int)lo, s));
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, s));
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[0][wave] = cnt;
+        red[1][wave] = lo;
+        red[2][wave] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        cnt = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+        lo = min(min(red[1][0], red[1][1]), min(red[1][2], red[1][3]));
+        hi = max(max(red[2][0], red[2][1]), max(red[2][2], red[2][3]));
+    }
+}
+
 // Grid-stride over the pixels, ONE set of atomics per workgroup: the three statistics are single words that every contribution has to
 // reach, and r02's profile of the 58-view loop showed the earlier one-set-per-wave form (10 000 waves x 3 same-address atomics at
 // 800x800) serialised in L2 for 339 us per view -- 7 % of a view, 20x the dilation kernel.  Integer count and ordered-uint min / max:
 // order-independent, so the results are unchanged.
 #define SN_MASK_VIS_BLOCKS 512
 __global__ __launch_bounds__(256) void sn_mask_visible_kernel(SnMaskParams p) {
-    __shared__ uint32_t red[3][4];
     const int64_t n = (int64_t)p.height * p.width;
     uint32_t cnt = 0u, lo = 0xffffffffu, hi = 0u;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -66,23 +92,8 @@ __global__ __launch_bounds__(256) void sn_mask_visible_kernel(SnMaskParams p) {
             hi = max(hi, od);
         }
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        cnt += (uint32_t)__shfl_xor((int)cnt, s);
-        lo = min(lo, (uint32_t)__shfl_xor((int)lo, s));
-        hi = max(hi, (uint32_t)__shfl_xor((int)hi, s));
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][wave] = cnt;
-        red[1][wave] = lo;
-        red[2][wave] = hi;
-    }
-    __syncthreads();
+    sn_mask_block_reduce(cnt, lo, hi);
     if (threadIdx.x == 0) {
-        cnt = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        lo = min(min(red[1][0], red[1][1]), min(red[1][2], red[1][3]));
-        hi = max(max(red[2][0], red[2][1]), max(red[2][2], red[2][3]));
         if (cnt) atomicAdd(&p.stats[0], cnt);
         if (lo != 0xffffffffu) {
             atomicMin(&p.stats[1], lo);
@@ -111,48 +122,64 @@ __global__ __launch_bounds__(64) void sn_mask_prefix_kernel(SnMaskParams p) {
     }
 }
 
+// is_visible == False (nothing in the visible mask): pixel i gets a zero mask and a zero condition (datasetgenerator.py:812-818, :746-752)
+SN_DEV bool sn_mask_nothing_visible(const SnMaskParams& p, int64_t i) {
+    if (p.stats[0] != 0) return false;
+    p.mask[i] = 0;
+    if (p.condition) p.condition[i] = 0.0f;
+    return true;
+}
+
+// the mask bit of pixel i: the visible mask, dilated by the ellipse if there is one
+SN_DEV bool sn_mask_dilated(const SnMaskParams& p, int64_t i) {
+    if (!p.dilate) return p.vis[i] != 0;
+    // cv2.dilate: dst(x,y) = max over set (i,j) of src(x + j - ax, y + i - ay); pixels outside the image do not contribute
+    const int y = (int)(i / p.width), x = (int)(i % p.width);
+    bool m = false;
+    for (int r = 0; r < p.el.kh && !m; ++r) {
+        const int yy = y + r - p.el.ay;
+        if (yy < 0 || yy >= p.height) continue;
+        const int a = max(x + p.el.j1[r] - p.el.ax, 0), b = min(x + p.el.j2[r] - p.el.ax, p.width);
+        if (a >= b) continue;
+        const int32_t* pr = p.prefix + (int64_t)yy * (p.width + 1);
+        m = pr[b] - pr[a] > 0;
+    }
+    return m;
+}
+
+// the depth normalisation (d - dmin) / range of a condition image: the manual pair, or the statistics of the visible kernel widened by
+// depth_radius.  torch.min / torch.max of an empty selection raise in the reference; here an empty selection (all visible depths <= 0)
+// leaves the sentinels, which map to -inf / +inf -> condition NaN-free but meaningless.  Not reachable with positive depths in the aabb
+// mode; the shape mode tests for it before it calls this.
+SN_DEV void sn_mask_depth_norm(const SnMaskParams& p, float& dmin, float& range) {
+#pragma clang fp contract(off)
+    if (p.has_manual_depth) {
+        dmin = p.manual_min;
+        range = p.manual_range;
+    } else {
+        dmin = sn_ordered_float(p.stats[1]) - p.depth_radius;
+        const float dmax = sn_ordered_float(p.stats[2]) + p.depth_radius;
+        range = dmax - dmin;
+    }
+}
+
+// 1 - torch.clamp(c, 0, 1).  torch.clamp keeps a NaN (the depth of a ray that missed render_aabb, inf / inf of an unbounded selection,
+// 0 * inf of a blend); fminf / fmaxf would drop it
+SN_DEV float sn_mask_one_minus_clamp(float c) {
+#pragma clang fp contract(off)
+    return 1.0f - (c != c ? c : fminf(fmaxf(c, 0.0f), 1.0f));
+}
+
 __global__ void sn_mask_condition_kernel(SnMaskParams p) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t n = (int64_t)p.height * p.width;
-    if (i >= n) return;
-    const uint32_t count = p.stats[0];
-    if (count == 0) {  // is_visible == False: zero mask, zero condition (datasetgenerator.py:812-818)
-        p.mask[i] = 0;
-        if (p.condition) p.condition[i] = 0.0f;
-        return;
-    }
-    const int y = (int)(i / p.width), x = (int)(i % p.width);
-    bool m = p.vis[i] != 0;
-    if (p.dilate) {
-        // cv2.dilate: dst(x,y) = max over set (i,j) of src(x + j - ax, y + i - ay); pixels outside the image do not contribute
-        m = false;
-        for (int r = 0; r < p.el.kh && !m; ++r) {
-            const int yy = y + r - p.el.ay;
-            if (yy < 0 || yy >= p.height) continue;
-            const int a = max(x + p.el.j1[r] - p.el.ax, 0), b = min(x + p.el.j2[r] - p.el.ax, p.width);
-            if (a >= b) continue;
-            const int32_t* pr = p.prefix + (int64_t)yy * (p.width + 1);
-            m = pr[b] - pr[a] > 0;
-        }
-    }
-    p.mask[i] = m ? 1 : 0;
+    if (i >= n || sn_mask_nothing_visible(p, i)) return;
+    p.mask[i] = sn_mask_dilated(p, i) ? 1 : 0;
     if (p.condition) {
 #pragma clang fp contract(off)
         float dmin, range;
-        if (p.has_manual_depth) {
-            dmin = p.manual_min;
-            range = p.manual_range;
-        } else {
-            // torch.min / torch.max of an empty selection raise in the reference; here an empty selection (all visible depths
-            // <= 0) leaves the sentinels, which map to -inf / +inf -> condition NaN-free but meaningless.  Not reachable with
-            // positive depths.
-            dmin = sn_ordered_float(p.stats[1]) - p.depth_radius;
-            const float dmax = sn_ordered_float(p.stats[2]) + p.depth_radius;
-            range = dmax - dmin;
-        }
-        const float dn = (p.depth[i] - dmin) / range;
-        // torch.clamp keeps a NaN (the depth of a ray that missed render_aabb, inf / inf of an unbounded selection); fminf / fmaxf would drop it
-        p.condition[i] = 1.0f - (dn != dn ? dn : fminf(fmaxf(dn, 0.0f), 1.0f));
+        sn_mask_depth_norm(p, dmin, range);
+        p.condition[i] = sn_mask_one_minus_clamp((p.depth[i] - dmin) / range);
     }
 }
 

@@ -1,14 +1,15 @@
 // sn_mesh.h -- "shape" masking mode: the proxy mesh's depth image and the shape-mode mask + condition
-// (/root/reference/signerf/datasetgenerator/datasetgenerator.py:711-754, signerf/renderer/renderer.py:64-196).  The reference draws the
-// mesh with pyrender (OpenGL / EGL) and reads the depth buffer back per view; here three kernels write the same z-depth image on the
+// (signerf/datasetgenerator/datasetgenerator.py:711-754, signerf/renderer/renderer.py:64-196 of the reference).  The reference draws the
+// mesh with pyrender (OpenGL / EGL) and reads the depth buffer back per view; here two kernels write the same z-depth image on the
 // device:
 //   M-a  triangle setup, one thread per triangle: model-view transform, back-face cull, near / far reject, a fixed-size record
 //        (three homogeneous edge vectors, the plane, the pixel bbox)
-//   M-b  per-tile depth, one 16x16 workgroup per screen tile: sweeps the triangles' bboxes in batches of 256, compacts the ones that
-//        touch the tile into LDS (ballot + prefix: fixed order), then every pixel tests coverage and keeps the nearest t in [znear, zfar]
+//   M-b  per-tile depth, one 16x16 workgroup per screen tile: sn_mesh_tile_sweep sweeps the triangles' bboxes in batches of 256, compacts
+//        the ones that touch the tile into LDS (ballot + prefix: fixed order), then every pixel tests coverage and keeps the nearest t in
+//        [znear, zfar].  The colour raster of sn_mesh_color.h (M-e) is the same sweep, instantiated to keep the winning triangle as well.
 // No atomics, no data-dependent workspace (its size is a function of the triangle count), bit-identical run to run.  Then the shape
-// mode's mask step:
-//   M-c  visible mask + count / min of the visible mesh depths / max of ALL mesh depths (same reduction shape as K-a of sn_mask.h)
+// mode's mask step, from the helpers of sn_mask.h:
+//   M-c  visible mask + count / min of the visible mesh depths / max of ALL mesh depths
 //   K-b  the dilation prefix counts (sn_mask_prefix_kernel, shared with the aabb mode)
 //   M-d  dilation + the shape condition 1 - clamp(vis * obj_norm + !vis * nerf_norm, 0, 1)
 #pragma once
@@ -116,22 +117,40 @@ __global__ __launch_bounds__(256) void sn_mesh_setup_kernel(SnMeshRasterParams p
     p.bbox[f] = make_uint2((uint32_t)x0 | ((uint32_t)y0 << 16), (uint32_t)x1 | ((uint32_t)y1 << 16));
 }
 
-__global__ __launch_bounds__(SN_MESH_BATCH) void sn_mesh_tile_kernel(SnMeshRasterParams p) {
+// What one thread of a tile workgroup knows after the sweep.  tri and e are kept by the kColor instantiation only.
+struct SnMeshTileHit {
+    int px, py;   // this thread's pixel
+    bool inside;  // ... is inside the image (the tiles of the last column / row hang over)
+    float z;      // nearest depth in [znear, zfar], INFINITY: nothing covers the pixel centre
+    int tri;      // the triangle of z, -1: none
+    float e[3];   // its three edge values at this pixel
+};
+
+// The per-tile loop of M-b and M-e, called by all SN_MESH_BATCH threads of the tile (blockIdx.x, blockIdx.y).  Ties in z go to the
+// triangle met first (strict z < best): batches and their LDS compaction are in triangle order, so the lowest index wins, as GL_LESS
+// keeps the first drawn.  z > 0 here, so for the depth alone the strict update keeps what fminf(best, z) would.
+template <bool kColor>
+SN_DEV SnMeshTileHit sn_mesh_tile_sweep(const SnMeshRasterParams& p) {
     __shared__ SnMeshTri s_rec[SN_MESH_BATCH];
     __shared__ int s_idx[SN_MESH_BATCH];
     __shared__ int s_wave[SN_MESH_BATCH / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tx0 = blockIdx.x * SN_MESH_TILE, ty0 = blockIdx.y * SN_MESH_TILE;
     const int tx1 = min(tx0 + SN_MESH_TILE, p.width) - 1, ty1 = min(ty0 + SN_MESH_TILE, p.height) - 1;
-    const int px = tx0 + (tid % SN_MESH_TILE), py = ty0 + (tid / SN_MESH_TILE);
+    SnMeshTileHit h;
+    h.px = tx0 + (tid % SN_MESH_TILE);
+    h.py = ty0 + (tid / SN_MESH_TILE);
+    h.inside = h.px <= tx1 && h.py <= ty1;
+    h.z = INFINITY;
+    h.tri = -1;
+    h.e[0] = h.e[1] = h.e[2] = 0.0f;
     float dx, dy;
     {
 #pragma clang fp contract(off)
-        dx = ((float)px + 0.5f - p.cx) / p.fx;
-        dy = -(((float)py + 0.5f - p.cy) / p.fy);
+        dx = ((float)h.px + 0.5f - p.cx) / p.fx;
+        dy = -(((float)h.py + 0.5f - p.cy) / p.fy);
     }
     const float dz = -1.0f;
-    float best = INFINITY;
     for (int base = 0; base < p.n_tris; base += SN_MESH_BATCH) {
         // 1. which triangles of this batch touch the tile: fixed-order compaction (ballot + wave prefix)
         const int f = base + tid;
@@ -154,7 +173,7 @@ __global__ __launch_bounds__(SN_MESH_BATCH) void sn_mesh_tile_kernel(SnMeshRaste
         // 2. stage the records of those triangles
         if (tid < total) s_rec[tid] = p.rec[s_idx[tid]];
         __syncthreads();
-        // 3. every pixel against every staged triangle (the loop bound is uniform over the workgroup)
+        // 3. every pixel against every staged triangle, in index order (the loop bound is uniform over the workgroup)
         for (int k = 0; k < total; ++k) {
             const SnMeshTri& t = s_rec[k];
             const float e0 = fmaf(t.e[0], dx, fmaf(t.e[1], dy, t.e[2] * dz));
@@ -163,13 +182,26 @@ __global__ __launch_bounds__(SN_MESH_BATCH) void sn_mesh_tile_kernel(SnMeshRaste
             const bool in = (e0 >= 0.0f && e1 >= 0.0f && e2 >= 0.0f) || (e0 <= 0.0f && e1 <= 0.0f && e2 <= 0.0f);
             if (in) {
                 const float nd = fmaf(t.n[0], dx, fmaf(t.n[1], dy, t.n[2] * dz));
-                const float z = t.nA / nd;  // NaN / inf for a ray in the plane: fails both comparisons below
-                if (z >= p.znear && z <= p.zfar) best = fminf(best, z);
+                const float z = t.nA / nd;  // NaN / inf for a ray in the plane: fails the comparisons below
+                if (z >= p.znear && z <= p.zfar && z < h.z) {
+                    h.z = z;
+                    if constexpr (kColor) {
+                        h.tri = s_idx[k];
+                        h.e[0] = e0;
+                        h.e[1] = e1;
+                        h.e[2] = e2;
+                    }
+                }
             }
         }
         __syncthreads();  // s_wave / s_idx / s_rec are rewritten by the next batch
     }
-    if (px <= tx1 && py <= ty1) p.depth[(int64_t)py * p.width + px] = best == INFINITY ? 0.0f : best;
+    return h;
+}
+
+__global__ __launch_bounds__(SN_MESH_BATCH) void sn_mesh_tile_kernel(SnMeshRasterParams p) {
+    const SnMeshTileHit h = sn_mesh_tile_sweep<false>(p);
+    if (h.inside) p.depth[(int64_t)h.py * p.width + h.px] = h.z == INFINITY ? 0.0f : h.z;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -182,7 +214,6 @@ struct SnShapeMaskParams {
 
 __global__ __launch_bounds__(256) void sn_shape_visible_kernel(SnShapeMaskParams sp) {
     const SnMaskParams& p = sp.m;
-    __shared__ uint32_t red[3][4];
     const int64_t n = (int64_t)p.height * p.width;
     uint32_t cnt = 0u, lo = 0xffffffffu, hi = 0u;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -195,23 +226,8 @@ __global__ __launch_bounds__(256) void sn_shape_visible_kernel(SnShapeMaskParams
         if (vis && (md * 1.0f > 0.0f)) lo = min(lo, om);  // depth[visible_mask * depth > 0]
         hi = max(hi, om);                                 // torch.max(depth): every pixel
     }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        cnt += (uint32_t)__shfl_xor((int)cnt, s);
-        lo = min(lo, (uint32_t)__shfl_xor((int)lo, s));
-        hi = max(hi, (uint32_t)__shfl_xor((int)hi, s));
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][wave] = cnt;
-        red[1][wave] = lo;
-        red[2][wave] = hi;
-    }
-    __syncthreads();
+    sn_mask_block_reduce(cnt, lo, hi);
     if (threadIdx.x == 0) {
-        cnt = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-        lo = min(min(red[1][0], red[1][1]), min(red[1][2], red[1][3]));
-        hi = max(max(red[2][0], red[2][1]), max(red[2][2], red[2][3]));
         if (cnt) atomicAdd(&p.stats[0], cnt);
         if (lo != 0xffffffffu) atomicMin(&p.stats[1], lo);
         atomicMax(&p.stats[2], hi);
@@ -224,44 +240,21 @@ __global__ void sn_shape_condition_kernel(SnShapeMaskParams sp) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t n = (int64_t)p.height * p.width;
     if (i >= n) return;
-    if (p.stats[0] == 0) {  // is_visible == False: zero mask, zero condition (:746-752)
-        p.mask[i] = 0;
-        if (p.condition) p.condition[i] = 0.0f;
-        return;
-    }
-    const int y = (int)(i / p.width), x = (int)(i % p.width);
+    if (sn_mask_nothing_visible(p, i)) return;
     const bool v = p.vis[i] != 0;
-    bool m = v;
-    if (p.dilate) {  // as sn_mask_condition_kernel
-        m = false;
-        for (int r = 0; r < p.el.kh && !m; ++r) {
-            const int yy = y + r - p.el.ay;
-            if (yy < 0 || yy >= p.height) continue;
-            const int a = max(x + p.el.j1[r] - p.el.ax, 0), b = min(x + p.el.j2[r] - p.el.ax, p.width);
-            if (a >= b) continue;
-            const int32_t* pr = p.prefix + (int64_t)yy * (p.width + 1);
-            m = pr[b] - pr[a] > 0;
-        }
-    }
-    p.mask[i] = m ? 1 : 0;
+    p.mask[i] = sn_mask_dilated(p, i) ? 1 : 0;
     if (!p.condition) return;
-    float dmin, range;
-    if (p.has_manual_depth) {
-        dmin = p.manual_min;
-        range = p.manual_range;
-    } else if (p.stats[1] == 0xffffffffu) {
+    if (!p.has_manual_depth && p.stats[1] == 0xffffffffu) {
         // something is visible but no visible pixel has a mesh depth > 0 (reachable with inverse_mask): the reference's torch.min of an
         // empty selection raises.  Defined here as an all-zero condition (the mask stays as computed).
         p.condition[i] = 0.0f;
         return;
-    } else {
-        dmin = sn_ordered_float(p.stats[1]) - p.depth_radius;
-        const float dmax = sn_ordered_float(p.stats[2]) + p.depth_radius;
-        range = dmax - dmin;
     }
+    float dmin, range;
+    sn_mask_depth_norm(p, dmin, range);
     const float on = (sp.mesh_depth[i] - dmin) / range;
     const float nn = (p.depth[i] - dmin) / range;
     // visible_mask * obj + (~visible_mask) * nerf: the multiplies stay (0 * NaN, 0 * inf = NaN poisons the pixel as in the reference)
     const float c = (v ? 1.0f : 0.0f) * on + (v ? 0.0f : 1.0f) * nn;
-    p.condition[i] = 1.0f - (c != c ? c : fminf(fmaxf(c, 0.0f), 1.0f));
+    p.condition[i] = sn_mask_one_minus_clamp(c);
 }

@@ -60,6 +60,28 @@ class DatasetGeneratorConfig:
     renderer: Optional[RendererConfig] = None
 
 
+def _mask_opts(mask_dialation, inverse_mask, manual_depth, additional_depth_radius) -> "_lib.SnMaskOpts":
+    """The ``SnMaskOpts`` of a mask step from the wrappers' keywords."""
+    opts = _lib.SnMaskOpts()
+    opts.inverse_mask = int(bool(inverse_mask))
+    if mask_dialation is not None:
+        # cv2.getStructuringElement takes (width, height)
+        opts.dilate_w, opts.dilate_h = int(mask_dialation[0]), int(mask_dialation[1])
+    opts.has_manual_depth = int(manual_depth is not None)
+    if manual_depth is not None:
+        opts.manual_min, opts.manual_max = float(manual_depth[0]), float(manual_depth[1])
+    opts.additional_depth_radius = float(additional_depth_radius)
+    return opts
+
+
+def _mask_buffers(lib, H: int, W: int, dev, with_condition: bool):
+    """(mask uint8, condition fp32 | None, workspace) of a mask step on `dev` (call under ``torch.cuda.device(dev)``)."""
+    mask = torch.empty((H, W, 1), dtype=torch.uint8, device=dev)
+    cond = torch.empty((H, W, 1), dtype=torch.float32, device=dev) if with_condition else None
+    ws = torch.empty(lib.sn_mask_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
+    return mask, cond, ws
+
+
 def aabb_mask_and_condition(depth: Tensor, rays_o: Tensor, rays_d: Tensor, aabb: Tensor, mask_dialation: Optional[Tuple[int, int]] = (50, 50),
                             inverse_mask: bool = False, manual_depth: Optional[Tuple[float, float]] = None,
                             additional_depth_radius: float = 0.1, with_condition: bool = True):
@@ -70,20 +92,10 @@ def aabb_mask_and_condition(depth: Tensor, rays_o: Tensor, rays_d: Tensor, aabb:
     dev = depth.device
     f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
     o, d, z = f32(rays_o), f32(rays_d), f32(depth)
-    opts = _lib.SnMaskOpts()
-    opts.inverse_mask = int(bool(inverse_mask))
-    if mask_dialation is not None:
-        # cv2.getStructuringElement takes (width, height)
-        opts.dilate_w, opts.dilate_h = int(mask_dialation[0]), int(mask_dialation[1])
-    opts.has_manual_depth = int(manual_depth is not None)
-    if manual_depth is not None:
-        opts.manual_min, opts.manual_max = float(manual_depth[0]), float(manual_depth[1])
-    opts.additional_depth_radius = float(additional_depth_radius)
+    opts = _mask_opts(mask_dialation, inverse_mask, manual_depth, additional_depth_radius)
     box = (C.c_float * 6)(*aabb.detach().to("cpu", torch.float32).reshape(-1).tolist())
     with torch.cuda.device(dev):
-        mask = torch.empty((H, W, 1), dtype=torch.uint8, device=dev)
-        cond = torch.empty((H, W, 1), dtype=torch.float32, device=dev) if with_condition else None
-        ws = torch.empty(lib.sn_mask_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
+        mask, cond, ws = _mask_buffers(lib, H, W, dev, with_condition)
         _lib.check(lib.sn_aabb_mask_condition(_lib.ptr(o), _lib.ptr(d), _lib.ptr(z), H, W, box, C.byref(opts), _lib.ptr(mask),
                                               _lib.ptr(cond), ws.data_ptr(), ws.numel(), _lib.current_stream()),
                    None, "sn_aabb_mask_condition")
@@ -107,19 +119,10 @@ def aabb_mask_and_condition_combined(depth: Tensor, rays_o: Tensor, rays_d: Tens
     if md.numel() != H * W or mc.dtype != torch.uint8 or tuple(mc.shape) != (H, W, 3):
         raise ValueError(f"mesh depth {tuple(mesh_depth.shape)} must be [H,W,1] and mesh colour {tuple(mesh_color.shape)} {mesh_color.dtype} "
                          f"[H,W,3] uint8 for a NeRF depth of {tuple(depth.shape)}")
-    opts = _lib.SnMaskOpts()
-    opts.inverse_mask = int(bool(inverse_mask))
-    if mask_dialation is not None:
-        opts.dilate_w, opts.dilate_h = int(mask_dialation[0]), int(mask_dialation[1])
-    opts.has_manual_depth = int(manual_depth is not None)
-    if manual_depth is not None:
-        opts.manual_min, opts.manual_max = float(manual_depth[0]), float(manual_depth[1])
-    opts.additional_depth_radius = float(additional_depth_radius)
+    opts = _mask_opts(mask_dialation, inverse_mask, manual_depth, additional_depth_radius)
     box = (C.c_float * 6)(*aabb.detach().to("cpu", torch.float32).reshape(-1).tolist())
     with torch.cuda.device(dev):
-        mask = torch.empty((H, W, 1), dtype=torch.uint8, device=dev)
-        cond = torch.empty((H, W, 1), dtype=torch.float32, device=dev) if with_condition else None
-        ws = torch.empty(lib.sn_mask_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
+        mask, cond, ws = _mask_buffers(lib, H, W, dev, with_condition)
         _lib.check(lib.sn_aabb_mask_condition_combined(_lib.ptr(o), _lib.ptr(d), _lib.ptr(z), H, W, box, C.byref(opts), _lib.ptr(md),
                                                        _lib.ptr(mc), _lib.ptr(mask), _lib.ptr(cond), ws.data_ptr(), ws.numel(),
                                                        _lib.current_stream()),
@@ -139,18 +142,9 @@ def shape_mask_and_condition(mesh_depth: Tensor, depth: Tensor, mask_dialation: 
     md, z = f32(mesh_depth), f32(depth)
     if md.numel() != H * W or z.numel() != H * W:
         raise ValueError(f"mesh depth {tuple(mesh_depth.shape)} and NeRF depth {tuple(depth.shape)} must both be [H,W,1]")
-    opts = _lib.SnMaskOpts()
-    opts.inverse_mask = int(bool(inverse_mask))
-    if mask_dialation is not None:
-        opts.dilate_w, opts.dilate_h = int(mask_dialation[0]), int(mask_dialation[1])
-    opts.has_manual_depth = int(manual_depth is not None)
-    if manual_depth is not None:
-        opts.manual_min, opts.manual_max = float(manual_depth[0]), float(manual_depth[1])
-    opts.additional_depth_radius = float(additional_depth_radius)
+    opts = _mask_opts(mask_dialation, inverse_mask, manual_depth, additional_depth_radius)
     with torch.cuda.device(dev):
-        mask = torch.empty((H, W, 1), dtype=torch.uint8, device=dev)
-        cond = torch.empty((H, W, 1), dtype=torch.float32, device=dev) if with_condition else None
-        ws = torch.empty(lib.sn_mask_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
+        mask, cond, ws = _mask_buffers(lib, H, W, dev, with_condition)
         _lib.check(lib.sn_shape_mask_condition(_lib.ptr(md), _lib.ptr(z), H, W, C.byref(opts), _lib.ptr(mask), _lib.ptr(cond), ws.data_ptr(),
                                                ws.numel(), _lib.current_stream()),
                    None, "sn_shape_mask_condition")

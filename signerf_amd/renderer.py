@@ -144,15 +144,20 @@ def model_view(c2w, pose: np.ndarray) -> np.ndarray:
     return (np.linalg.inv(m) @ pose)[:3]
 
 
+def _raster_args(mv, znear: float, zfar: float, cull_back_faces: bool):
+    """(``SnMeshRasterOpts``, the model-view as ``c_float * 12``) of a raster call."""
+    opts = _lib.SnMeshRasterOpts()
+    opts.znear, opts.zfar, opts.cull_back_faces = float(znear), float(zfar), int(bool(cull_back_faces))
+    return opts, (C.c_float * 12)(*np.asarray(mv, dtype=np.float64).reshape(12).tolist())
+
+
 def raster_depth(vertices: Tensor, triangles: Tensor, mv, fx: float, fy: float, cx: float, cy: float, height: int, width: int,
                  znear: float = ZNEAR, zfar: float = ZFAR, cull_back_faces: bool = True, out: Optional[Tensor] = None) -> Tensor:
     """``sn_mesh_raster_depth``: vertices [V,3] fp32 / triangles [F,3] int32 on the GPU, mv: camera-from-object [3,4] (host) ->
     z-depth [H,W,1] fp32 on the GPU, 0 where the mesh is not drawn."""
     lib = _lib.load()
     dev = vertices.device
-    opts = _lib.SnMeshRasterOpts()
-    opts.znear, opts.zfar, opts.cull_back_faces = float(znear), float(zfar), int(bool(cull_back_faces))
-    m = (C.c_float * 12)(*np.asarray(mv, dtype=np.float64).reshape(12).tolist())
+    opts, m = _raster_args(mv, znear, zfar, cull_back_faces)
     F = int(triangles.shape[0])
     with torch.cuda.device(dev):
         depth = out if out is not None else torch.empty((height, width, 1), dtype=torch.float32, device=dev)
@@ -191,14 +196,12 @@ def raster_color(vertices: Tensor, triangles: Tensor, mv, fx: float, fy: float, 
     if vertex_colors is not None and (vertex_colors.dtype != torch.uint8 or tuple(vertex_colors.shape) != (int(vertices.shape[0]), 4)):
         raise ValueError(f"vertex_colors must be [V,4] uint8 with V = {int(vertices.shape[0])}, got {tuple(vertex_colors.shape)} "
                          f"{vertex_colors.dtype}")
-    opts = _lib.SnMeshRasterOpts()
-    opts.znear, opts.zfar, opts.cull_back_faces = float(znear), float(zfar), int(bool(cull_back_faces))
+    opts, m = _raster_args(mv, znear, zfar, cull_back_faces)
     shade = _lib.SnMeshShadeOpts()
     shade.base_color[:] = [float(x) for x in base_color]
     shade.ambient[:] = [float(x) for x in ambient]
     shade.background[:] = [float(x) for x in background]
     shade.gamma = int(bool(gamma))
-    m = (C.c_float * 12)(*np.asarray(mv, dtype=np.float64).reshape(12).tolist())
     F = int(triangles.shape[0])
     with torch.cuda.device(dev):
         color = torch.empty((height, width, 3), dtype=torch.uint8, device=dev)
