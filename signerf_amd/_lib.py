@@ -16,6 +16,7 @@ SN_OK, SN_ERR_INVALID, SN_ERR_HIP, SN_ERR_STATE, SN_ERR_WORKSPACE = 0, 1, 2, 3, 
 SN_ABI_VERSION = 6   # include/signerf_hip.h "ABI evolution": load() refuses a library built with another one
 SN_MESH_ABI_VERSION = 1   # include/signerf_hip_mesh.h, checked the same way
 SN_MESH_COLOR_ABI_VERSION = 1   # include/signerf_hip_mesh_color.h, checked the same way
+SN_MESH_RAYS_ABI_VERSION = 1   # include/signerf_hip_mesh_rays.h, checked the same way
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # SIGNERF_HIP_LIB: load another build of the library (A/B experiments with tools/ab_lib.sh); the default is the in-tree build
@@ -228,6 +229,25 @@ MESH_COLOR_SIGNATURES = {
                                                   _FP, _FP, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
+
+class SnMeshRaysOpts(_Sized):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("znear", C.c_float),
+        ("zfar", C.c_float),
+        ("cull_back_faces", C.c_int32),
+    ]
+
+
+# The companion header include/signerf_hip_mesh_rays.h (the mesh along the camera's own rays): every symbol it declares
+# (tests/test_mesh_rays_host.py checks them).
+MESH_RAYS_SIGNATURES = {
+    "sn_mesh_rays_abi_version": (C.c_int, []),
+    "sn_mesh_accel_bytes": (C.c_size_t, [C.c_int64]),
+    "sn_mesh_cast_rays": (C.c_int, [_FP, _FP, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_size_t, _FP, C.c_int64, _FP,
+                                    C.c_int64, C.POINTER(SnMeshRaysOpts), C.POINTER(SnMeshShadeOpts), _FP, _FP, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lock = threading.Lock()
 
@@ -251,7 +271,8 @@ def load() -> C.CDLL:
             lib = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover
             raise SignerfHipError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in list(SIGNATURES.items()) + list(MESH_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + (list(MESH_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items())
+                                         + list(MESH_RAYS_SIGNATURES.items())):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise SignerfHipError(f"{LIB_PATH} does not export {name}: it was built from another include/signerf_hip.h -- rebuild it "
@@ -269,6 +290,10 @@ def load() -> C.CDLL:
         if got != SN_MESH_COLOR_ABI_VERSION:
             raise SignerfHipError(f"{LIB_PATH} reports SN_MESH_COLOR_ABI_VERSION {got}, this binding was written for "
                                   f"{SN_MESH_COLOR_ABI_VERSION}: rebuild the library")
+        got = lib.sn_mesh_rays_abi_version()
+        if got != SN_MESH_RAYS_ABI_VERSION:
+            raise SignerfHipError(f"{LIB_PATH} reports SN_MESH_RAYS_ABI_VERSION {got}, this binding was written for "
+                                  f"{SN_MESH_RAYS_ABI_VERSION}: rebuild the library")
         _lib = lib
         return lib
 

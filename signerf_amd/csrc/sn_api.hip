@@ -3,6 +3,7 @@
 #include "../../include/signerf_hip.h"
 #include "../../include/signerf_hip_mesh.h"
 #include "../../include/signerf_hip_mesh_color.h"
+#include "../../include/signerf_hip_mesh_rays.h"
 
 #include <hip/hip_runtime.h>
 
@@ -23,6 +24,7 @@
 #include "sn_mask.h"
 #include "sn_mesh.h"
 #include "sn_mesh_color.h"
+#include "sn_mesh_rays.h"
 #include "sn_normals.h"
 #include "sn_proposal.h"
 #include "sn_stage.h"
@@ -2422,6 +2424,19 @@ size_t sn_mesh_color_workspace_bytes(int64_t n_triangles, int32_t height, int32_
     return sn_mesh_workspace_bytes(n_triangles, height, width);
 }
 
+// SnMeshShadeOpts (adopted) -> the kernels' SnMeshShade; false: a component is not finite
+static bool fill_mesh_shade(const SnMeshShadeOpts& so, const uint8_t* vertex_colors, SnMeshShade& s) {
+    s.vertex_colors = vertex_colors;
+    for (int c = 0; c < 3; ++c) {
+        if (!std::isfinite(so.base_color[c]) || !std::isfinite(so.ambient[c]) || !std::isfinite(so.background[c])) return false;
+        s.base[c] = so.base_color[c];
+        s.ambient[c] = so.ambient[c];
+        s.background[c] = so.background[c];
+    }
+    s.gamma = so.gamma != 0;
+    return true;
+}
+
 int sn_mesh_raster_color(const float* vertices, int64_t n_vertices, const uint8_t* vertex_colors, const int32_t* triangles,
                          int64_t n_triangles, const float* model_view, float fx, float fy, float cx, float cy, int32_t height, int32_t width,
                          const SnMeshRasterOpts* opts, const SnMeshShadeOpts* shade, float* depth, uint8_t* color, void* workspace,
@@ -2434,16 +2449,8 @@ int sn_mesh_raster_color(const float* vertices, int64_t n_vertices, const uint8_
         return rc;
     SnMeshShadeOpts so;
     if (int rc = adopt_struct(nullptr, shade, kMeshShadeOptsMin, so, "sn_mesh_raster_color: SnMeshShadeOpts")) return rc;
-    for (int c = 0; c < 3; ++c)
-        if (!std::isfinite(so.base_color[c]) || !std::isfinite(so.ambient[c]) || !std::isfinite(so.background[c]))
-            return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_color: base_color, ambient and background must be finite");
-    cp.vertex_colors = vertex_colors;
-    for (int c = 0; c < 3; ++c) {
-        cp.base[c] = so.base_color[c];
-        cp.ambient[c] = so.ambient[c];
-        cp.background[c] = so.background[c];
-    }
-    cp.gamma = so.gamma != 0;
+    if (!fill_mesh_shade(so, vertex_colors, cp.s))
+        return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_color: base_color, ambient and background must be finite");
     cp.color = color;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(sn_mesh_tile_color_kernel, launch_mesh_setup(cp.r, st), dim3(SN_MESH_BATCH), 0, st, cp);
@@ -2469,6 +2476,64 @@ int sn_aabb_mask_condition_combined(const float* origins, const float* direction
     hipLaunchKernelGGL(sn_mask_visible_kernel, mask_visible_grid(n), dim3(256), 0, st, p);
     if (p.dilate) hipLaunchKernelGGL(sn_mask_prefix_kernel, dim3((unsigned)height), dim3(64), 0, st, p);
     hipLaunchKernelGGL(sn_mask_condition_combined_kernel, per_pixel_grid(n), dim3(256), 0, st, cp);
+    return end_launches(who);
+}
+
+
+// ---- include/signerf_hip_mesh_rays.h: the mesh along the camera's own rays -----------------------------------------------------------
+int sn_mesh_rays_abi_version(void) { return SN_MESH_RAYS_ABI_VERSION; }
+
+constexpr size_t kMeshRaysOptsMin = sizeof(SnMeshRaysOpts);  // the first layout
+#define SN_MESH_RAYS_MAX_TRIS ((int64_t)1 << 26)  // a leaf reference packs first * 8 + count into 31 bits
+
+size_t sn_mesh_accel_bytes(int64_t n_triangles) {
+    if (n_triangles < 0 || n_triangles > SN_MESH_RAYS_MAX_TRIS) return 0;
+    const size_t f = (size_t)n_triangles;
+    return sizeof(SnMeshAccelHeader) + std::max<size_t>(f, 1) * sizeof(SnMeshAccelNode) + f * sizeof(SnMeshAccelTri);
+}
+
+int sn_mesh_cast_rays(const float* origins, const float* directions, int32_t height, int32_t width, const float* forward,
+                      const void* accel, size_t accel_bytes, const int32_t* triangles, int64_t n_triangles, const uint8_t* vertex_colors,
+                      int64_t n_vertices, const SnMeshRaysOpts* opts, const SnMeshShadeOpts* shade, float* depth, uint8_t* color,
+                      SnStream stream) {
+    const std::string who = "sn_mesh_cast_rays";
+    if (!origins || !directions || !forward || !accel || !opts || !depth || height <= 0 || width <= 0 || height > SN_MESH_MAX_DIM ||
+        width > SN_MESH_MAX_DIM || n_triangles < 0 || n_triangles > SN_MESH_RAYS_MAX_TRIS || n_vertices < 0 || (color && (!shade || !triangles)))
+        return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
+    SnMeshRaysOpts o;
+    if (int rc = adopt_struct(nullptr, opts, kMeshRaysOptsMin, o, (who + ": SnMeshRaysOpts").c_str())) return rc;
+    if (!(o.znear > 0.0f) || !(o.zfar > o.znear) || !std::isfinite(o.zfar)) return fail(nullptr, SN_ERR_INVALID, who + ": need 0 < znear < zfar < inf");
+    if (accel_bytes != sn_mesh_accel_bytes(n_triangles) || ((uintptr_t)accel & 15u) != 0)
+        return fail(nullptr, SN_ERR_INVALID, who + ": accel must be a 16-byte-aligned blob of sn_mesh_accel_bytes(n_triangles) bytes");
+    const double fn = std::sqrt((double)forward[0] * forward[0] + (double)forward[1] * forward[1] + (double)forward[2] * forward[2]);
+    if (!std::isfinite(fn) || !(fn > 0.0)) return fail(nullptr, SN_ERR_INVALID, who + ": forward must be a finite non-zero vector");
+    SnMeshRaysParams p;
+    memset(&p, 0, sizeof(p));
+    if (color) {
+        SnMeshShadeOpts so;
+        if (int rc = adopt_struct(nullptr, shade, kMeshShadeOptsMin, so, (who + ": SnMeshShadeOpts").c_str())) return rc;
+        if (!fill_mesh_shade(so, vertex_colors, p.s)) return fail(nullptr, SN_ERR_INVALID, who + ": base_color, ambient and background must be finite");
+    }
+    p.origins = origins;
+    p.directions = directions;
+    p.height = height;
+    p.width = width;
+    for (int k = 0; k < 3; ++k) p.fwd[k] = (float)(forward[k] / fn);
+    p.znear = o.znear;
+    p.zfar = o.zfar;
+    p.cull = o.cull_back_faces != 0;
+    p.accel = (const uint8_t*)accel;
+    p.n_tris = (int32_t)n_triangles;
+    p.tris = triangles;
+    p.n_vertices = n_vertices;
+    p.depth = depth;
+    p.color = color;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16));
+    if (color)
+        hipLaunchKernelGGL(sn_mesh_rays_kernel<true>, grid, dim3(SN_RAYS_BLOCK), 0, st, p);
+    else
+        hipLaunchKernelGGL(sn_mesh_rays_kernel<false>, grid, dim3(SN_RAYS_BLOCK), 0, st, p);
     return end_launches(who);
 }
 

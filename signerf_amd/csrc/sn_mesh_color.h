@@ -16,13 +16,18 @@
 #include "sn_mask.h"
 #include "sn_mesh.h"
 
-struct SnMeshColorParams {
-    SnMeshRasterParams r;         // r.depth may be NULL here
+// The shading both mesh kernels share (this header's M-e and the ray cast of sn_mesh_rays.h).
+struct SnMeshShade {
     const uint8_t* vertex_colors; // [V,4] RGBA8, or NULL (COLOR_0 = 1)
     float base[3];                // material baseColorFactor.rgb
     float ambient[3];
     float background[3];          // in [0, 1], written without gamma
     int gamma;                    // != 0: pow(x, 1 / 2.2) before the quantisation
+};
+
+struct SnMeshColorParams {
+    SnMeshRasterParams r;         // r.depth may be NULL here
+    SnMeshShade s;
     uint8_t* color;               // [H,W,3] out
 };
 
@@ -32,40 +37,53 @@ SN_DEV uint8_t sn_unorm8(float x) {
     return (uint8_t)(int)(x * 255.0f + 0.5f);
 }
 
+// One pixel's colour o[0..2]: the background for tri < 0, else triangle `tri` of `tris` shaded at the barycentric weights b0, b1, b2 of
+// its corners: interpolated vertex colour x base colour x ambient, optional gamma 1/2.2, unorm8.
+SN_DEV void sn_mesh_shade_pixel(const SnMeshShade& s, const int32_t* tris, int tri, float b0, float b1, float b2, uint8_t* o) {
+    float rgb[3];
+    if (tri < 0) {
+        for (int c = 0; c < 3; ++c) rgb[c] = s.background[c];
+    } else {
+#pragma clang fp contract(off)
+        float col[3] = {1.0f, 1.0f, 1.0f};
+        if (s.vertex_colors) {
+            const int32_t* t = tris + (int64_t)tri * 3;
+            const uint8_t* ca = s.vertex_colors + (int64_t)t[0] * 4;
+            const uint8_t* cb = s.vertex_colors + (int64_t)t[1] * 4;
+            const uint8_t* cc = s.vertex_colors + (int64_t)t[2] * 4;
+            for (int c = 0; c < 3; ++c)
+                col[c] = b0 * ((float)ca[c] / 255.0f) + b1 * ((float)cb[c] / 255.0f) + b2 * ((float)cc[c] / 255.0f);
+        }
+        for (int c = 0; c < 3; ++c) {
+            float x = s.ambient[c] * (s.base[c] * col[c]);
+            if (s.gamma) x = powf(fmaxf(x, 0.0f), 1.0f / 2.2f);
+            rgb[c] = x;
+        }
+    }
+    o[0] = sn_unorm8(rgb[0]);
+    o[1] = sn_unorm8(rgb[1]);
+    o[2] = sn_unorm8(rgb[2]);
+}
+
 __global__ __launch_bounds__(SN_MESH_BATCH) void sn_mesh_tile_color_kernel(SnMeshColorParams cp) {
     const SnMeshRasterParams& p = cp.r;
     const SnMeshTileHit h = sn_mesh_tile_sweep<true>(p);
     if (!h.inside) return;
     const int64_t pix = (int64_t)h.py * p.width + h.px;
     if (p.depth) p.depth[pix] = h.z == INFINITY ? 0.0f : h.z;
-    float rgb[3];
-    if (h.tri < 0) {
-        for (int c = 0; c < 3; ++c) rgb[c] = cp.background[c];
-    } else {
+    float b0 = 1.0f, b1 = 0.0f, b2 = 0.0f;
+    if (h.tri >= 0 && cp.s.vertex_colors) {
 #pragma clang fp contract(off)
-        float col[3] = {1.0f, 1.0f, 1.0f};
-        if (cp.vertex_colors) {
-            // the centre is inside (or on an edge of) the winner: e0..e2 share a sign and their sum is not 0 unless the triangle is seen
-            // edge-on, where a degenerate weight falls back to the first corner
-            const float s = h.e[0] + h.e[1] + h.e[2];
-            const float b0 = s != 0.0f ? h.e[0] / s : 1.0f, b1 = s != 0.0f ? h.e[1] / s : 0.0f, b2 = s != 0.0f ? h.e[2] / s : 0.0f;
-            const int32_t* tri = p.tris + (int64_t)h.tri * 3;
-            const uint8_t* ca = cp.vertex_colors + (int64_t)tri[0] * 4;
-            const uint8_t* cb = cp.vertex_colors + (int64_t)tri[1] * 4;
-            const uint8_t* cc = cp.vertex_colors + (int64_t)tri[2] * 4;
-            for (int c = 0; c < 3; ++c)
-                col[c] = b0 * ((float)ca[c] / 255.0f) + b1 * ((float)cb[c] / 255.0f) + b2 * ((float)cc[c] / 255.0f);
-        }
-        for (int c = 0; c < 3; ++c) {
-            float x = cp.ambient[c] * (cp.base[c] * col[c]);
-            if (cp.gamma) x = powf(fmaxf(x, 0.0f), 1.0f / 2.2f);
-            rgb[c] = x;
+        // the centre is inside (or on an edge of) the winner: e0..e2 share a sign and their sum is not 0 unless the triangle is seen
+        // edge-on, where a degenerate weight falls back to the first corner
+        const float s = h.e[0] + h.e[1] + h.e[2];
+        if (s != 0.0f) {
+            b0 = h.e[0] / s;
+            b1 = h.e[1] / s;
+            b2 = h.e[2] / s;
         }
     }
-    uint8_t* o = cp.color + pix * 3;
-    o[0] = sn_unorm8(rgb[0]);
-    o[1] = sn_unorm8(rgb[1]);
-    o[2] = sn_unorm8(rgb[2]);
+    sn_mesh_shade_pixel(cp.s, p.tris, h.tri, b0, b1, b2, cp.color + pix * 3);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -151,6 +151,12 @@ def shape_mask_and_condition(mesh_depth: Tensor, depth: Tensor, mask_dialation: 
     return mask.bool(), cond
 
 
+def _lens_rays(renderer, ray_bundle) -> dict:
+    """The keyword that hands the view's rays to a lens-aware renderer (``RendererConfig.lens = "camera"``), so that it generates none of
+    its own; nothing for the pinhole raster, which takes the camera alone."""
+    return {"ray_bundle": ray_bundle} if getattr(getattr(renderer, "config", None), "lens", "pinhole") == "camera" else {}
+
+
 def render_camera(config: DatasetGeneratorConfig, graph, camera, with_mask: bool = True, with_condition: bool = True,
                   renderer: Optional[Renderer] = None, combine_shape_with_depth: Optional[bool] = None):
     """One camera: rgb, mask, condition (datasetgenerator.py:677-820).  `camera`: a 0-dim ``Cameras`` of this package or any object with
@@ -173,7 +179,7 @@ def render_camera(config: DatasetGeneratorConfig, graph, camera, with_mask: bool
     if config.masking_mode == "shape":
         if renderer is None:
             raise ValueError("Renderer is None but masking mode is shape")
-        _, mesh_depth = renderer.render_camera(camera)
+        _, mesh_depth = renderer.render_camera(camera, **_lens_rays(renderer, camera_ray_bundle))
         mask, cond = shape_mask_and_condition(mesh_depth, depth, config.mask_dialation, config.inverse_mask, config.manual_depth,
                                               config.additional_depth_radius, with_condition)
         if not with_condition:
@@ -186,7 +192,7 @@ def render_camera(config: DatasetGeneratorConfig, graph, camera, with_mask: bool
     if combine and with_condition:
         if renderer is None:
             raise ValueError("Renderer is None but masking mode is shape")   # (the reference's message, :796)
-        mesh_color, mesh_depth = renderer.render_camera(camera, with_color=True)
+        mesh_color, mesh_depth = renderer.render_camera(camera, with_color=True, **_lens_rays(renderer, camera_ray_bundle))
         mask, cond = aabb_mask_and_condition_combined(depth, camera_ray_bundle.origins, camera_ray_bundle.directions, aabb, mesh_depth,
                                                       mesh_color, config.mask_dialation, config.inverse_mask, config.manual_depth,
                                                       config.additional_depth_radius)

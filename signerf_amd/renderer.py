@@ -6,6 +6,10 @@ one offscreen renderer and one host read-back per view.  Here the mesh is parsed
 centres (DESIGN.md "Shape masking mode" lists what differs from pyrender's multisampled 24-bit depth buffer).  ``render_camera`` returns
 ``(None, depth)``; with ``with_color=True`` it returns ``(color, depth)`` from one call of ``sn_mesh_raster_color``, the colour shaded as
 pyrender shades a mesh under the reference's ambient-only light (``shade_defaults``; the constants are UNPINNED).
+
+That raster is a pinhole, as pyrender's camera is, whatever lens the NeRF's camera has.  ``RendererConfig.lens = "camera"`` draws the mesh
+along the camera's own rays instead (``sn_mesh_cast_rays``; DESIGN.md "Lens-aware proxy mesh"): a bounding-volume hierarchy over the posed
+mesh is built once in ``setup`` (``build_accel``), uploaded once per device, and every view is one ray-cast launch.
 """
 
 from __future__ import annotations
@@ -40,6 +44,13 @@ class RendererConfig:
     object_path: str = field(default_factory=lambda: "models/bunny.obj")
     cull_back_faces: bool = True
     """pyrender draws a mesh without a double-sided material with GL_BACK culling; False draws both sides"""
+    lens: str = "pinhole"
+    """not in the reference.  "pinhole": the mesh is rasterised through an ideal pinhole with the camera's fx, fy, cx, cy, as pyrender
+    draws it -- distortion and camera type are ignored.  "camera": the mesh is drawn along the camera's own rays (OPENCV distortion,
+    FISHEYE, EQUIRECTANGULAR), so that it lines up with the NeRF image of the same camera"""
+
+
+LENSES = ("pinhole", "camera")
 
 
 def load_obj(path, with_colors: bool = False):
@@ -215,11 +226,124 @@ def raster_color(vertices: Tensor, triangles: Tensor, mv, fx: float, fy: float, 
     return color, depth
 
 
+ACCEL_LEAF_MAX = 4   # SN_RAYS_LEAF_MAX of csrc/sn_mesh_rays.h
+ACCEL_MAX_DEPTH = 32  # SN_RAYS_STACK
+_ACCEL_MAGIC, _ACCEL_VERSION = 0x31524D53, 1
+
+
+def _accel_leaf(first: int, count: int) -> int:
+    return -(1 + first * 8 + count)
+
+
+def build_accel(vertices: np.ndarray, triangles: np.ndarray) -> np.ndarray:
+    """The acceleration blob of ``sn_mesh_cast_rays`` (layout: csrc/sn_mesh_rays.h) for POSED vertices [V,3] float32 and triangles [F,3]
+    int32 -> uint8 [sn_mesh_accel_bytes(F)].  A binary bounding-volume hierarchy, split at the median of the triangle centroids along the
+    axis of their largest extent (so its depth is about log2 F), leaves of at most 4 triangles; an inner node holds the boxes of its two
+    children, widened by a few ulp.  Every triangle is in exactly one leaf; one with an index outside the vertices or a non-finite corner
+    is stored with all corners at the origin (never hit), as the rasteriser drops it."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+    F = int(t.shape[0])
+    ok = ((t >= 0) & (t < v.shape[0])).all(1)
+    corners = np.zeros((F, 3, 3), dtype=np.float32)
+    corners[ok] = v[t[ok]]
+    corners[~np.isfinite(corners).all((1, 2))] = 0.0
+    lo, hi = corners.min(1).astype(np.float64), corners.max(1).astype(np.float64)
+    cen = corners.astype(np.float64).mean(1)
+    order = np.arange(F)
+    cap = max(F, 1)
+    boxes = np.zeros((cap, 12), dtype=np.float32)
+    boxes[:, 0:3] = boxes[:, 6:9] = np.inf      # an inverted box: no child
+    boxes[:, 3:6] = boxes[:, 9:12] = -np.inf
+    child = np.full((cap, 2), _accel_leaf(0, 0), dtype=np.int32)
+    n_nodes = 1
+    # (start, end, node that owns the range's box, side of it, depth); the root's two sides are the halves of everything
+    if F <= ACCEL_LEAF_MAX:
+        todo = [(0, F, 0, 0, 1)] if F else []
+    else:
+        todo = [(0, F, -1, 0, 0)]
+    while todo:
+        s, e, parent, side, depth = todo.pop()
+        if depth > ACCEL_MAX_DEPTH:
+            raise ValueError(f"the hierarchy over {F} triangles is deeper than {ACCEL_MAX_DEPTH} levels")
+        idx = order[s:e]
+        if parent >= 0:
+            blo, bhi = lo[idx].min(0), hi[idx].max(0)
+            pad = 1e-6 * max(float(np.abs(blo).max()), float(np.abs(bhi).max())) + 1e-30
+            boxes[parent, 6 * side:6 * side + 3] = np.nextafter((blo - pad).astype(np.float32), np.float32(-np.inf))
+            boxes[parent, 6 * side + 3:6 * side + 6] = np.nextafter((bhi + pad).astype(np.float32), np.float32(np.inf))
+        if e - s <= ACCEL_LEAF_MAX:
+            child[parent, side] = _accel_leaf(s, e - s)
+            continue
+        if parent >= 0:
+            node = n_nodes
+            n_nodes += 1
+            child[parent, side] = node
+        else:
+            node = 0
+        c = cen[idx]
+        axis = int(np.argmax(c.max(0) - c.min(0)))
+        m = (e - s) // 2
+        order[s:e] = idx[np.argpartition(c[:, axis], m)]
+        todo.append((s, s + m, node, 0, depth + 1))
+        todo.append((s + m, e, node, 1, depth + 1))
+    header = np.zeros(16, dtype=np.uint32)
+    header[:4] = [_ACCEL_MAGIC, _ACCEL_VERSION, F, n_nodes]
+    nodes = np.zeros((cap, 16), dtype=np.float32)
+    nodes[:, :12] = boxes
+    nodes[:, 12:14] = child.view(np.float32)
+    recs = np.zeros((F, 12), dtype=np.float32)
+    recs[:, :9] = corners[order].reshape(F, 9)
+    recs[:, 9] = order.astype(np.int32).view(np.float32)
+    return np.concatenate([header.view(np.uint8), nodes.reshape(-1).view(np.uint8), recs.reshape(-1).view(np.uint8)])
+
+
+def cast_rays(origins: Tensor, directions: Tensor, forward, accel: Tensor, n_triangles: int, height: int, width: int,
+              triangles: Optional[Tensor] = None, vertex_colors: Optional[Tensor] = None, n_vertices: int = 0, with_color: bool = False,
+              base_color=PYRENDER_DEFAULT_BASE_COLOR, ambient=REFERENCE_AMBIENT, background=PYRENDER_BACKGROUND, gamma: bool = True,
+              znear: float = ZNEAR, zfar: float = ZFAR, cull_back_faces: bool = True) -> Tuple[Optional[Tensor], Tensor]:
+    """``sn_mesh_cast_rays``: world-space origins / directions of height * width rays (fp32, on the GPU, row-major: what ``generate_rays``
+    returns), forward: the camera's viewing axis (3 host floats), accel: ``build_accel``'s blob on the GPU -> (color [H,W,3] uint8 or None,
+    z-depth [H,W,1] fp32), 0 / the background where the mesh is not drawn.  with_color needs triangles [F,3] int32 on the GPU (and takes
+    vertex_colors [V,4] uint8, n_vertices = V)."""
+    lib = _lib.load()
+    dev = accel.device
+    n = int(height) * int(width)
+    if origins.numel() != 3 * n or directions.numel() != 3 * n:
+        raise ValueError(f"the ray bundle holds {origins.numel() // 3} origins and {directions.numel() // 3} directions, the camera has "
+                         f"{height} x {width} = {n} pixels")
+    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+    o, d = f32(origins), f32(directions)
+    if with_color and triangles is None:
+        raise ValueError("with_color needs the triangles")
+    if vertex_colors is not None and (vertex_colors.dtype != torch.uint8 or tuple(vertex_colors.shape) != (int(n_vertices), 4)):
+        raise ValueError(f"vertex_colors must be [V,4] uint8 with V = {int(n_vertices)}, got {tuple(vertex_colors.shape)} {vertex_colors.dtype}")
+    opts = _lib.SnMeshRaysOpts()
+    opts.znear, opts.zfar, opts.cull_back_faces = float(znear), float(zfar), int(bool(cull_back_faces))
+    shade = _lib.SnMeshShadeOpts()
+    shade.base_color[:] = [float(x) for x in base_color]
+    shade.ambient[:] = [float(x) for x in ambient]
+    shade.background[:] = [float(x) for x in background]
+    shade.gamma = int(bool(gamma))
+    fwd = (C.c_float * 3)(*[float(x) for x in forward])
+    with torch.cuda.device(dev):
+        depth = torch.empty((height, width, 1), dtype=torch.float32, device=dev)
+        color = torch.empty((height, width, 3), dtype=torch.uint8, device=dev) if with_color else None
+        vc = None if vertex_colors is None else vertex_colors.contiguous()
+        _lib.check(lib.sn_mesh_cast_rays(_lib.ptr(o), _lib.ptr(d), int(height), int(width), fwd, _lib.ptr(accel), accel.numel(),
+                                         _lib.ptr(triangles), int(n_triangles), _lib.ptr(vc), int(n_vertices), C.byref(opts),
+                                         C.byref(shade) if with_color else None, _lib.ptr(depth), _lib.ptr(color), _lib.current_stream()),
+                   None, "sn_mesh_cast_rays")
+    return color, depth
+
+
 class Renderer:
     """``Renderer`` of the reference (renderer.py:43-196): the depth it feeds the shape masking mode and the colour + depth that
     ``combine_shape_with_depth`` pastes into the aabb condition."""
 
     def __init__(self, config: RendererConfig, device="cuda") -> None:
+        if config.lens not in LENSES:
+            raise ValueError(f"RendererConfig.lens = {config.lens!r}: must be one of {', '.join(LENSES)}")
         self.config = config
         self.device = device
         self.position, self.rotation, self.scale, self.color = config.position, config.rotation, config.scale, config.color
@@ -229,12 +353,20 @@ class Renderer:
         self._host_colors: Optional[Tuple[Optional[np.ndarray]]] = None   # ([V,4] uint8 vertex colours or None,) once read
         self._uploaded: Dict[str, Tuple[Tensor, Tensor]] = {}
         self._uploaded_colors: Dict[str, Optional[Tensor]] = {}
+        self._host_accel: Optional[np.ndarray] = None   # lens == "camera": build_accel's blob of the posed mesh
+        self._uploaded_accel: Dict[str, Tensor] = {}
 
     def setup(self) -> None:
-        """Parse the mesh and compute its pose (renderer.py:64-121).  Unlike the reference, a missing or non-OBJ file raises here."""
+        """Parse the mesh and compute its pose (renderer.py:64-121).  Unlike the reference, a missing or non-OBJ file raises here.
+        With ``lens="camera"`` the acceleration structure of the posed mesh is built here too, once."""
         self._host_mesh = load_obj(self.object_path)
         self.pose = object_pose(self.config)
         self._host_colors, self._uploaded, self._uploaded_colors = None, {}, {}
+        self._host_accel, self._uploaded_accel = None, {}
+        if self.config.lens == "camera":
+            v, f = self._host_mesh
+            world = (v.astype(np.float64) @ self.pose[:3, :3].T + self.pose[:3, 3]).astype(np.float32)
+            self._host_accel = build_accel(world, f)
 
     @property
     def num_triangles(self) -> int:
@@ -265,10 +397,22 @@ class Renderer:
             self._uploaded_colors[key] = None if c is None else torch.from_numpy(c).to(verts.device)
         return self._uploaded_colors[key]
 
-    def render_camera(self, camera, with_color: bool = False) -> Tuple[Optional[Tensor], Tensor]:
+    def accel_on(self, device) -> Tensor:
+        """``build_accel``'s blob on `device` (``lens="camera"``), uploaded the first time a view of that device is rendered."""
+        verts, _ = self.mesh_on(device)
+        if self._host_accel is None:
+            raise RuntimeError('Renderer.setup() built no acceleration structure: RendererConfig.lens was not "camera" then')
+        key = str(verts.device)
+        if key not in self._uploaded_accel:
+            self._uploaded_accel[key] = torch.from_numpy(self._host_accel).to(verts.device)
+        return self._uploaded_accel[key]
+
+    def render_camera(self, camera, with_color: bool = False, ray_bundle=None) -> Tuple[Optional[Tensor], Tensor]:
         """-> (None, depth [H,W,1] fp32 on the camera's device); with_color: (color [H,W,3] uint8, depth), shaded as pyrender shades the
         mesh under the reference's ambient light (``shade_defaults``).  Intrinsics and pose come from the camera's host mirror (no device
-        sync); pinhole only -- distortion and camera type are ignored, as pyrender's IntrinsicsCamera ignores them."""
+        sync).  ``lens="pinhole"`` (the default): distortion and camera type are ignored, as pyrender's IntrinsicsCamera ignores them, and
+        so is `ray_bundle`.  ``lens="camera"``: the mesh along the camera's rays -- `ray_bundle` (the H x W bundle the caller has already
+        generated for this camera) or, without one, ``generate_rays(camera_indices=0)``; a bundle of another size raises ValueError."""
         from .cameras import Cameras
 
         cam = Cameras.from_cameras(camera)
@@ -277,6 +421,14 @@ class Renderer:
         W, H = int(host[16]), int(host[17])
         dev = cam.device if cam.device.type == "cuda" else torch.device(self.device)
         verts, tris = self.mesh_on(dev)
+        if self.config.lens == "camera":
+            accel = self.accel_on(dev)
+            if ray_bundle is None:
+                ray_bundle = (cam if cam.device.type == "cuda" else cam.to(dev)).generate_rays(camera_indices=0)
+            vc = self.colors_on(dev) if with_color else None
+            forward = (-host[2], -host[6], -host[10])   # a nerfstudio camera looks down its -z axis
+            return cast_rays(ray_bundle.origins, ray_bundle.directions, forward, accel, int(tris.shape[0]), H, W, tris, vc, int(verts.shape[0]),
+                             with_color, znear=ZNEAR, zfar=ZFAR, cull_back_faces=self.config.cull_back_faces, **shade_defaults(vc is not None))
         mv = model_view(host[:12], self.pose)
         if not with_color:
             return None, raster_depth(verts, tris, mv, fx, fy, cx, cy, H, W, ZNEAR, ZFAR, self.config.cull_back_faces)

@@ -17,6 +17,13 @@ the plain one (sn_aabb_mask_condition); flag_share = what the flag adds to a vie
 NeRF render.
 
     python tools/shape_mask_bench.py --combine [--size 800] [--reps 50] [--json OUT]
+
+--rays times the lens-aware proxy mesh (RendererConfig.lens = "camera"): the ray cast of the bunny-sized mesh (sn_mesh_cast_rays, depth
+only and colour + depth, over the view's own ray bundle) beside the pinhole raster and the NeRF render of the same view, per view and as
+medians; the acceleration structure's host build time and size are reported once.  cast_over_nerf must stay below 1: the generator
+keeps two frames in flight, so a mask step longer than the render would bound the view loop.
+
+    python tools/shape_mask_bench.py --rays [--size 800] [--reps 50] [--json OUT]
 """
 import argparse
 import json
@@ -30,7 +37,7 @@ import torch  # noqa: E402
 
 from signerf_amd import Cameras, scene  # noqa: E402
 from signerf_amd.datasetgenerator import aabb_mask_and_condition, aabb_mask_and_condition_combined, shape_mask_and_condition  # noqa: E402
-from signerf_amd.renderer import RendererConfig, model_view, object_pose, raster_color, raster_depth  # noqa: E402
+from signerf_amd.renderer import RendererConfig, build_accel, cast_rays, model_view, object_pose, raster_color, raster_depth  # noqa: E402
 
 
 def icosphere(subdivisions):
@@ -71,6 +78,7 @@ def main():
     ap.add_argument("--nerf-reps", type=int, default=10)
     ap.add_argument("--json", default=None)
     ap.add_argument("--combine", action="store_true", help="time combine_shape_with_depth (see the module docstring)")
+    ap.add_argument("--rays", action="store_true", help="time the lens-aware ray cast beside the raster and the NeRF render")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     S = a.size
@@ -83,6 +91,8 @@ def main():
     pose = object_pose(RendererConfig(scale=[0.015, 0.015, 0.015]))   # radius 0.15, about the bunny's extent at the default scale
     if a.combine:
         return combine(a, model, cams, pose, dev)
+    if a.rays:
+        return rays(a, model, cams, pose, dev)
     meshes = {"bunny_5120": icosphere(4), "big_1.3M": icosphere(8)}
     rows = []
     for view in range(0, 8, 2):
@@ -153,6 +163,48 @@ def combine(a, model, cams, pose, dev):
     summary = {name: {k: float(np.median([r[k] for r in rows if r["mesh"] == name])) for k in keys} for name in ("bunny_5120", "closeup_5120")}
     out = {"size": S, "reps": a.reps, "gpu": torch.cuda.get_device_name(0), "leg": "combine", "median_over_views": summary, "rows": rows}
     print(json.dumps({"median_over_views": summary}))
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+
+
+def rays(a, model, cams, pose, dev):
+    import time
+
+    S = a.size
+    v, f = icosphere(4)
+    vt, ft = torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev)
+    world = (v.astype(np.float64) @ pose[:3, :3].T + pose[:3, 3]).astype(np.float32)
+    t0 = time.perf_counter()
+    blob = build_accel(world, f)
+    build_s = time.perf_counter() - t0
+    accel = torch.from_numpy(blob).to(dev)
+    rows = []
+    for view in range(0, 8, 2):
+        cam = cams[view]
+        bundle = cam.generate_rays(0, aabb_box=model.render_aabb)
+        nerf_ms = timed(lambda: model.get_outputs_for_camera_ray_bundle(bundle), a.nerf_reps, 2)
+        o, d = bundle.origins.contiguous(), bundle.directions.contiguous()
+        host = cam._host[0].tolist()
+        fwd = (-host[2], -host[6], -host[10])
+        mv = model_view(host[:12], pose)
+        intr = (host[12], host[13], host[14], host[15], S, S)
+        r_ms = timed(lambda: raster_depth(vt, ft, mv, *intr), a.reps, a.warmup)
+        rc_ms = timed(lambda: raster_color(vt, ft, mv, *intr), a.reps, a.warmup)
+        c_ms = timed(lambda: cast_rays(o, d, fwd, accel, f.shape[0], S, S), a.reps, a.warmup)
+        cc_ms = timed(lambda: cast_rays(o, d, fwd, accel, f.shape[0], S, S, ft, None, v.shape[0], with_color=True), a.reps, a.warmup)
+        zc, zr = cast_rays(o, d, fwd, accel, f.shape[0], S, S)[1], raster_depth(vt, ft, mv, *intr)
+        rows.append({"view": view, "mesh": "bunny_5120", "faces": int(f.shape[0]), "raster_ms": round(r_ms, 4), "raster_color_ms": round(rc_ms, 4),
+                     "cast_ms": round(c_ms, 4), "cast_color_ms": round(cc_ms, 4), "nerf_render_ms": round(nerf_ms, 3),
+                     "cast_over_raster": round(c_ms / r_ms, 3), "cast_over_nerf": round(c_ms / nerf_ms, 4),
+                     "mesh_coverage": round(float((zc > 0).float().mean()), 4),
+                     "coverage_differs_px": int(((zc > 0) != (zr > 0)).sum())})
+        print(json.dumps(rows[-1]), flush=True)
+    keys = ("raster_ms", "raster_color_ms", "cast_ms", "cast_color_ms", "nerf_render_ms", "cast_over_raster", "cast_over_nerf", "mesh_coverage")
+    summary = {"bunny_5120": {k: float(np.median([r[k] for r in rows])) for k in keys}}
+    out = {"size": S, "reps": a.reps, "gpu": torch.cuda.get_device_name(0), "leg": "rays", "accel_build_host_s": round(build_s, 4),
+           "accel_bytes": int(blob.size), "median_over_views": summary, "rows": rows}
+    print(json.dumps({"accel_build_host_s": out["accel_build_host_s"], "accel_bytes": out["accel_bytes"], "median_over_views": summary}))
     if a.json:
         with open(a.json, "w") as fh:
             json.dump(out, fh, indent=1)
