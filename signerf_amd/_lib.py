@@ -17,6 +17,7 @@ SN_ABI_VERSION = 6   # include/signerf_hip.h "ABI evolution": load() refuses a l
 SN_MESH_ABI_VERSION = 1   # include/signerf_hip_mesh.h, checked the same way
 SN_MESH_COLOR_ABI_VERSION = 1   # include/signerf_hip_mesh_color.h, checked the same way
 SN_MESH_RAYS_ABI_VERSION = 1   # include/signerf_hip_mesh_rays.h, checked the same way
+SN_MESH_MATERIAL_ABI_VERSION = 1   # include/signerf_hip_mesh_material.h, checked the same way
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # SIGNERF_HIP_LIB: load another build of the library (A/B experiments with tools/ab_lib.sh); the default is the in-tree build
@@ -248,6 +249,46 @@ MESH_RAYS_SIGNATURES = {
                                     C.c_int64, C.POINTER(SnMeshRaysOpts), C.POINTER(SnMeshShadeOpts), _FP, _FP, C.c_void_p]),
 }
 
+
+class SnMeshMaterial(C.Structure):
+    """The frozen 32-byte material record (the kernels read it from device memory)."""
+
+    _fields_ = [
+        ("base_color", C.c_float * 4),
+        ("texel_offset", C.c_uint32),
+        ("tex_width", C.c_int32),
+        ("tex_height", C.c_int32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class SnMeshMaterials(_Sized):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_materials", C.c_int32),
+        ("materials", C.c_void_p),
+        ("host_materials", C.POINTER(SnMeshMaterial)),
+        ("triangle_material", C.c_void_p),
+        ("corner_uv", C.c_void_p),
+        ("texels", C.c_void_p),
+        ("texel_bytes", C.c_uint64),
+        ("texture_srgb", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+# The companion header include/signerf_hip_mesh_material.h (the mesh's colour image shaded with its .mtl materials): every symbol it
+# declares (tests/test_mesh_material_host.py checks them).
+MESH_MATERIAL_SIGNATURES = {
+    "sn_mesh_material_abi_version": (C.c_int, []),
+    "sn_mesh_raster_color_materials": (C.c_int, [_FP, C.c_int64, C.POINTER(SnMeshMaterials), _FP, C.c_int64, C.POINTER(C.c_float), C.c_float,
+                                                 C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.POINTER(SnMeshRasterOpts),
+                                                 C.POINTER(SnMeshShadeOpts), _FP, _FP, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sn_mesh_cast_rays_materials": (C.c_int, [_FP, _FP, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_size_t, _FP, C.c_int64,
+                                              C.POINTER(SnMeshMaterials), C.c_int64, C.POINTER(SnMeshRaysOpts), C.POINTER(SnMeshShadeOpts), _FP,
+                                              _FP, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lock = threading.Lock()
 
@@ -272,7 +313,7 @@ def load() -> C.CDLL:
         except OSError as e:  # pragma: no cover
             raise SignerfHipError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in list(SIGNATURES.items()) + (list(MESH_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items())
-                                         + list(MESH_RAYS_SIGNATURES.items())):
+                                         + list(MESH_RAYS_SIGNATURES.items()) + list(MESH_MATERIAL_SIGNATURES.items())):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise SignerfHipError(f"{LIB_PATH} does not export {name}: it was built from another include/signerf_hip.h -- rebuild it "
@@ -294,6 +335,10 @@ def load() -> C.CDLL:
         if got != SN_MESH_RAYS_ABI_VERSION:
             raise SignerfHipError(f"{LIB_PATH} reports SN_MESH_RAYS_ABI_VERSION {got}, this binding was written for "
                                   f"{SN_MESH_RAYS_ABI_VERSION}: rebuild the library")
+        got = lib.sn_mesh_material_abi_version()
+        if got != SN_MESH_MATERIAL_ABI_VERSION:
+            raise SignerfHipError(f"{LIB_PATH} reports SN_MESH_MATERIAL_ABI_VERSION {got}, this binding was written for "
+                                  f"{SN_MESH_MATERIAL_ABI_VERSION}: rebuild the library")
         _lib = lib
         return lib
 

@@ -4,6 +4,7 @@
 #include "../../include/signerf_hip_mesh.h"
 #include "../../include/signerf_hip_mesh_color.h"
 #include "../../include/signerf_hip_mesh_rays.h"
+#include "../../include/signerf_hip_mesh_material.h"
 
 #include <hip/hip_runtime.h>
 
@@ -25,6 +26,7 @@
 #include "sn_mesh.h"
 #include "sn_mesh_color.h"
 #include "sn_mesh_rays.h"
+#include "sn_mesh_material.h"
 #include "sn_normals.h"
 #include "sn_proposal.h"
 #include "sn_stage.h"
@@ -2492,13 +2494,15 @@ size_t sn_mesh_accel_bytes(int64_t n_triangles) {
     return sizeof(SnMeshAccelHeader) + std::max<size_t>(f, 1) * sizeof(SnMeshAccelNode) + f * sizeof(SnMeshAccelTri);
 }
 
-int sn_mesh_cast_rays(const float* origins, const float* directions, int32_t height, int32_t width, const float* forward,
-                      const void* accel, size_t accel_bytes, const int32_t* triangles, int64_t n_triangles, const uint8_t* vertex_colors,
-                      int64_t n_vertices, const SnMeshRaysOpts* opts, const SnMeshShadeOpts* shade, float* depth, uint8_t* color,
-                      SnStream stream) {
-    const std::string who = "sn_mesh_cast_rays";
+// What the two ray casts share, for the entry point `who`: the checks of the rays, the blob, SnMeshRaysOpts and (with a colour image)
+// SnMeshShadeOpts, and the SnMeshRaysParams.
+static int begin_cast_rays(const std::string& who, const float* origins, const float* directions, int32_t height, int32_t width,
+                           const float* forward, const void* accel, size_t accel_bytes, const int32_t* triangles, int64_t n_triangles,
+                           const uint8_t* vertex_colors, int64_t n_vertices, const SnMeshRaysOpts* opts, const SnMeshShadeOpts* shade,
+                           float* depth, uint8_t* color, bool need_triangles, SnMeshRaysParams& p) {
     if (!origins || !directions || !forward || !accel || !opts || !depth || height <= 0 || width <= 0 || height > SN_MESH_MAX_DIM ||
-        width > SN_MESH_MAX_DIM || n_triangles < 0 || n_triangles > SN_MESH_RAYS_MAX_TRIS || n_vertices < 0 || (color && (!shade || !triangles)))
+        width > SN_MESH_MAX_DIM || n_triangles < 0 || n_triangles > SN_MESH_RAYS_MAX_TRIS || n_vertices < 0 ||
+        (color && (!shade || (need_triangles && !triangles))))
         return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
     SnMeshRaysOpts o;
     if (int rc = adopt_struct(nullptr, opts, kMeshRaysOptsMin, o, (who + ": SnMeshRaysOpts").c_str())) return rc;
@@ -2507,7 +2511,6 @@ int sn_mesh_cast_rays(const float* origins, const float* directions, int32_t hei
         return fail(nullptr, SN_ERR_INVALID, who + ": accel must be a 16-byte-aligned blob of sn_mesh_accel_bytes(n_triangles) bytes");
     const double fn = std::sqrt((double)forward[0] * forward[0] + (double)forward[1] * forward[1] + (double)forward[2] * forward[2]);
     if (!std::isfinite(fn) || !(fn > 0.0)) return fail(nullptr, SN_ERR_INVALID, who + ": forward must be a finite non-zero vector");
-    SnMeshRaysParams p;
     memset(&p, 0, sizeof(p));
     if (color) {
         SnMeshShadeOpts so;
@@ -2528,12 +2531,104 @@ int sn_mesh_cast_rays(const float* origins, const float* directions, int32_t hei
     p.n_vertices = n_vertices;
     p.depth = depth;
     p.color = color;
+    return SN_OK;
+}
+
+static dim3 cast_rays_grid(int32_t height, int32_t width) { return dim3((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16)); }
+
+int sn_mesh_cast_rays(const float* origins, const float* directions, int32_t height, int32_t width, const float* forward,
+                      const void* accel, size_t accel_bytes, const int32_t* triangles, int64_t n_triangles, const uint8_t* vertex_colors,
+                      int64_t n_vertices, const SnMeshRaysOpts* opts, const SnMeshShadeOpts* shade, float* depth, uint8_t* color,
+                      SnStream stream) {
+    const std::string who = "sn_mesh_cast_rays";
+    SnMeshRaysParams p;
+    if (int rc = begin_cast_rays(who, origins, directions, height, width, forward, accel, accel_bytes, triangles, n_triangles, vertex_colors,
+                                 n_vertices, opts, shade, depth, color, true, p))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16));
     if (color)
-        hipLaunchKernelGGL(sn_mesh_rays_kernel<true>, grid, dim3(SN_RAYS_BLOCK), 0, st, p);
+        hipLaunchKernelGGL(sn_mesh_rays_kernel<true>, cast_rays_grid(height, width), dim3(SN_RAYS_BLOCK), 0, st, p);
     else
-        hipLaunchKernelGGL(sn_mesh_rays_kernel<false>, grid, dim3(SN_RAYS_BLOCK), 0, st, p);
+        hipLaunchKernelGGL(sn_mesh_rays_kernel<false>, cast_rays_grid(height, width), dim3(SN_RAYS_BLOCK), 0, st, p);
+    return end_launches(who);
+}
+
+
+// ---- include/signerf_hip_mesh_material.h: the mesh's colour image shaded with its materials -------------------------------------------
+int sn_mesh_material_abi_version(void) { return SN_MESH_MATERIAL_ABI_VERSION; }
+
+constexpr size_t kMeshMaterialsMin = sizeof(SnMeshMaterials);  // the first layout
+static_assert(sizeof(SnMeshMaterial) == sizeof(SnMeshMaterialRec), "the public record is the kernels' record");
+
+// SnMeshMaterials (checked against its host copy of the records) -> the kernels' SnMeshMaterialSet
+static int adopt_materials(const std::string& who, const SnMeshMaterials* materials, int64_t n_triangles, SnMeshMaterialSet& m) {
+    if (!materials) return fail(nullptr, SN_ERR_INVALID, who + ": materials is NULL");
+    SnMeshMaterials a;
+    if (int rc = adopt_struct(nullptr, materials, kMeshMaterialsMin, a, (who + ": SnMeshMaterials").c_str())) return rc;
+    if (a.n_materials < 1 || a.n_materials > 65535) return fail(nullptr, SN_ERR_INVALID, who + ": n_materials must be in [1, 65535]");
+    if (!a.materials || !a.host_materials || (n_triangles > 0 && !a.triangle_material))
+        return fail(nullptr, SN_ERR_INVALID, who + ": materials, host_materials and triangle_material must not be NULL");
+    if (((uintptr_t)a.materials & 15u) != 0 || ((uintptr_t)a.corner_uv & 7u) != 0 || ((uintptr_t)a.texels & 3u) != 0)
+        return fail(nullptr, SN_ERR_INVALID, who + ": materials must be 16-byte, corner_uv 8-byte and texels 4-byte aligned");
+    if (a.texel_bytes > 0 && !a.texels) return fail(nullptr, SN_ERR_INVALID, who + ": texels is NULL but texel_bytes is not 0");
+    const uint64_t n_texels = a.texel_bytes / 4u;
+    for (int32_t k = 0; k < a.n_materials; ++k) {
+        const SnMeshMaterial& r = a.host_materials[k];
+        const std::string which = who + ": material " + std::to_string(k);
+        for (int c = 0; c < 4; ++c)
+            if (!std::isfinite(r.base_color[c])) return fail(nullptr, SN_ERR_INVALID, which + ": base_color must be finite");
+        if (r.tex_width == 0 && r.tex_height == 0) continue;
+        if (r.tex_width < 1 || r.tex_height < 1 || r.tex_width > SN_MATERIAL_MAX_SIDE || r.tex_height > SN_MATERIAL_MAX_SIDE)
+            return fail(nullptr, SN_ERR_INVALID, which + ": a texture side must be in [1, 16384] (or both 0: no texture)");
+        if ((uint64_t)r.texel_offset + (uint64_t)r.tex_width * (uint64_t)r.tex_height > n_texels)
+            return fail(nullptr, SN_ERR_INVALID, which + ": its texture ends beyond the texel blob (texel_bytes too small)");
+    }
+    m.materials = (const SnMeshMaterialRec*)a.materials;
+    m.triangle_material = a.triangle_material;
+    m.corner_uv = a.corner_uv;
+    m.texels = (const uint32_t*)a.texels;
+    m.n_texels = n_texels;
+    m.n_materials = a.n_materials;
+    m.texture_srgb = a.texture_srgb != 0;
+    return SN_OK;
+}
+
+int sn_mesh_raster_color_materials(const float* vertices, int64_t n_vertices, const SnMeshMaterials* materials, const int32_t* triangles,
+                                   int64_t n_triangles, const float* model_view, float fx, float fy, float cx, float cy, int32_t height,
+                                   int32_t width, const SnMeshRasterOpts* opts, const SnMeshShadeOpts* shade, float* depth, uint8_t* color,
+                                   void* workspace, size_t workspace_bytes, SnStream stream) {
+    const std::string who = "sn_mesh_raster_color_materials";
+    SnMeshMaterialColorParams cp;
+    memset(&cp, 0, sizeof(cp));
+    if (n_triangles < 0) return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
+    if (int rc = adopt_materials(who, materials, n_triangles, cp.m)) return rc;
+    SnMeshShadeOpts so;
+    if (!shade) return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
+    if (int rc = adopt_struct(nullptr, shade, kMeshShadeOptsMin, so, (who + ": SnMeshShadeOpts").c_str())) return rc;
+    if (!fill_mesh_shade(so, nullptr, cp.s)) return fail(nullptr, SN_ERR_INVALID, who + ": base_color, ambient and background must be finite");
+    if (int rc = begin_raster(who, color != nullptr, vertices, n_vertices, triangles, n_triangles, model_view, fx, fy, cx, cy, height, width, opts,
+                              depth, workspace, workspace_bytes, cp.r))
+        return rc;
+    cp.color = color;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(sn_mesh_tile_material_kernel, launch_mesh_setup(cp.r, st), dim3(SN_MESH_BATCH), 0, st, cp);
+    return end_launches(who);
+}
+
+int sn_mesh_cast_rays_materials(const float* origins, const float* directions, int32_t height, int32_t width, const float* forward,
+                                const void* accel, size_t accel_bytes, const int32_t* triangles, int64_t n_triangles,
+                                const SnMeshMaterials* materials, int64_t n_vertices, const SnMeshRaysOpts* opts, const SnMeshShadeOpts* shade,
+                                float* depth, uint8_t* color, SnStream stream) {
+    const std::string who = "sn_mesh_cast_rays_materials";
+    SnMeshMaterialRaysParams mp;
+    memset(&mp, 0, sizeof(mp));
+    if (!color || !shade || n_triangles < 0) return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
+    if (int rc = adopt_materials(who, materials, n_triangles, mp.m)) return rc;
+    if (int rc = begin_cast_rays(who, origins, directions, height, width, forward, accel, accel_bytes, triangles, n_triangles, nullptr, n_vertices,
+                                 opts, shade, depth, color, false, mp.r))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(sn_mesh_rays_material_kernel, cast_rays_grid(height, width), dim3(SN_RAYS_BLOCK), 0, st, mp);
     return end_launches(who);
 }
 

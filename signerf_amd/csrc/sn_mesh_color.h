@@ -37,6 +37,15 @@ SN_DEV uint8_t sn_unorm8(float x) {
     return (uint8_t)(int)(x * 255.0f + 0.5f);
 }
 
+// The tail every shading shares (vertex colours here, materials in sn_mesh_material.h): one channel's ambient x (base colour x col) with
+// the optional gamma 1/2.2, before the quantisation.  col: COLOR_0, or the texture value.
+SN_DEV float sn_mesh_shade_channel(float ambient, float base, float col, int gamma) {
+#pragma clang fp contract(off)
+    float x = ambient * (base * col);
+    if (gamma) x = powf(fmaxf(x, 0.0f), 1.0f / 2.2f);
+    return x;
+}
+
 // One pixel's colour o[0..2]: the background for tri < 0, else triangle `tri` of `tris` shaded at the barycentric weights b0, b1, b2 of
 // its corners: interpolated vertex colour x base colour x ambient, optional gamma 1/2.2, unorm8.
 SN_DEV void sn_mesh_shade_pixel(const SnMeshShade& s, const int32_t* tris, int tri, float b0, float b1, float b2, uint8_t* o) {
@@ -54,11 +63,7 @@ SN_DEV void sn_mesh_shade_pixel(const SnMeshShade& s, const int32_t* tris, int t
             for (int c = 0; c < 3; ++c)
                 col[c] = b0 * ((float)ca[c] / 255.0f) + b1 * ((float)cb[c] / 255.0f) + b2 * ((float)cc[c] / 255.0f);
         }
-        for (int c = 0; c < 3; ++c) {
-            float x = s.ambient[c] * (s.base[c] * col[c]);
-            if (s.gamma) x = powf(fmaxf(x, 0.0f), 1.0f / 2.2f);
-            rgb[c] = x;
-        }
+        for (int c = 0; c < 3; ++c) rgb[c] = sn_mesh_shade_channel(s.ambient[c], s.base[c], col[c], s.gamma);
     }
     o[0] = sn_unorm8(rgb[0]);
     o[1] = sn_unorm8(rgb[1]);

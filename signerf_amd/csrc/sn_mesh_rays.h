@@ -114,17 +114,18 @@ SN_DEV void sn_ray_leaf(const SnMeshAccelTri* tris, int child, const float* o, c
     }
 }
 
-template <bool kColor>
-__global__ __launch_bounds__(SN_RAYS_BLOCK) void sn_mesh_rays_kernel(SnMeshRaysParams p) {
+// The walk of M-r, called by all SN_RAYS_BLOCK threads of the workgroup (blockIdx.x, blockIdx.y): this thread's ray (false: its pixel
+// is outside the image), f = direction . forward, and the nearest drawn hit.  The kernels below and the one of sn_mesh_material.h differ
+// in what they write for it.
+SN_DEV bool sn_mesh_rays_walk(const SnMeshRaysParams& p, int64_t& ray, float& f, SnRayHit& h) {
     __shared__ int s_stack[SN_RAYS_STACK][SN_RAYS_BLOCK];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int px = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), py = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-    if (px >= p.width || py >= p.height) return;  // (no barrier below)
-    const int64_t ray = (int64_t)py * p.width + px;
+    if (px >= p.width || py >= p.height) return false;  // (no barrier below)
+    ray = (int64_t)py * p.width + px;
     const float o[3] = {p.origins[ray * 3 + 0], p.origins[ray * 3 + 1], p.origins[ray * 3 + 2]};
     const float d[3] = {p.directions[ray * 3 + 0], p.directions[ray * 3 + 1], p.directions[ray * 3 + 2]};
-    const float f = d[0] * p.fwd[0] + d[1] * p.fwd[1] + d[2] * p.fwd[2];
-    SnRayHit h;
+    f = d[0] * p.fwd[0] + d[1] * p.fwd[1] + d[2] * p.fwd[2];
     h.t = INFINITY;
     h.u = h.v = 0.0f;
     h.tri = -1;
@@ -172,6 +173,15 @@ __global__ __launch_bounds__(SN_RAYS_BLOCK) void sn_mesh_rays_kernel(SnMeshRaysP
             }
         }
     }
+    return true;
+}
+
+template <bool kColor>
+__global__ __launch_bounds__(SN_RAYS_BLOCK) void sn_mesh_rays_kernel(SnMeshRaysParams p) {
+    int64_t ray;
+    float f;
+    SnRayHit h;
+    if (!sn_mesh_rays_walk(p, ray, f, h)) return;
     const bool drawn = h.tri >= 0;
     p.depth[ray] = drawn ? h.t * f : 0.0f;
     if constexpr (kColor) {

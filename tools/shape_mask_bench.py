@@ -24,6 +24,14 @@ medians; the acceleration structure's host build time and size are reported once
 keeps two frames in flight, so a mask step longer than the render would bound the view loop.
 
     python tools/shape_mask_bench.py --rays [--size 800] [--reps 50] [--json OUT]
+
+--materials times the proxy-mesh materials (RendererConfig.materials = "mtl"): the textured colour raster (sn_mesh_raster_color_materials:
+three materials over thirds of the mesh, a 64 x 64 and a 96 x 40 texture, spherical uv) beside the depth raster and the colour raster
+without and with vertex colours, for bunny_5120 and closeup_5120, and the textured ray cast (sn_mesh_cast_rays_materials) beside the
+vertex-colour ray cast for bunny_5120 (the close-up is a model-view of the raster only).  The vertex-colour path is the nearest
+existing one: the same sweep or walk, an epilogue with three gathers instead of about twelve loads.
+
+    python tools/shape_mask_bench.py --materials [--size 800] [--reps 50] [--json OUT]
 """
 import argparse
 import json
@@ -79,6 +87,7 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--combine", action="store_true", help="time combine_shape_with_depth (see the module docstring)")
     ap.add_argument("--rays", action="store_true", help="time the lens-aware ray cast beside the raster and the NeRF render")
+    ap.add_argument("--materials", action="store_true", help="time the textured colour raster and ray cast beside the vertex-colour ones")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     S = a.size
@@ -93,6 +102,8 @@ def main():
         return combine(a, model, cams, pose, dev)
     if a.rays:
         return rays(a, model, cams, pose, dev)
+    if a.materials:
+        return materials(a, model, cams, pose, dev)
     meshes = {"bunny_5120": icosphere(4), "big_1.3M": icosphere(8)}
     rows = []
     for view in range(0, 8, 2):
@@ -205,6 +216,79 @@ def rays(a, model, cams, pose, dev):
     out = {"size": S, "reps": a.reps, "gpu": torch.cuda.get_device_name(0), "leg": "rays", "accel_build_host_s": round(build_s, 4),
            "accel_bytes": int(blob.size), "median_over_views": summary, "rows": rows}
     print(json.dumps({"accel_build_host_s": out["accel_build_host_s"], "accel_bytes": out["accel_bytes"], "median_over_views": summary}))
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(out, fh, indent=1)
+
+
+def _bench_materials(v, f):
+    """Three materials over thirds of the mesh (two textured, one Kd only), spherical per-corner uv that cross the wrap seam, and
+    position-dependent vertex colours for the path it is compared with."""
+    from signerf_amd.renderer import ObjMaterial, pack_materials
+
+    def texture(w, h, seed):
+        x, y = np.meshgrid((np.arange(w) + 0.5) / w, (np.arange(h) + 0.5) / h)
+        t = np.full((h, w, 4), 255, dtype=np.uint8)
+        for c in range(3):
+            t[..., c] = np.round(255 * (0.2 + 0.8 * (0.5 + 0.5 * np.sin(2 * np.pi * ((1 + c % 2) * x + y) + c + seed)))).astype(np.uint8)
+        return t
+
+    p = v.astype(np.float64)
+    r = np.maximum(np.linalg.norm(p, axis=1), 1e-12)
+    cu = (np.arctan2(p[:, 1], p[:, 0]) / (2 * np.pi) + 0.5)[f]
+    cw = (1.0 - np.arccos(np.clip(p[:, 2] / r, -1, 1)) / np.pi)[f]
+    cu = np.where((cu.max(1, keepdims=True) - cu) > 0.5, cu + 1.0, cu)
+    uv = np.stack([cu, cw], -1).astype(np.float32)
+    tm = np.minimum(np.arange(f.shape[0]) * 3 // f.shape[0], 2).astype(np.int32)
+    mats = [ObjMaterial("square", (0.9, 0.8, 1.0), "a", texture(64, 64, 0)), ObjMaterial("oblong", (1.0, 1.0, 1.0), "b", texture(96, 40, 1)),
+            ObjMaterial("plain", (0.55, 0.35, 0.75))]
+    vc = np.full((v.shape[0], 4), 255, dtype=np.uint8)
+    vc[:, :3] = np.round(255 * (0.2 + 0.8 * (0.5 + 0.5 * np.sin(3.0 * p + 0.5)))).astype(np.uint8)
+    return pack_materials(uv, tm, mats), vc
+
+
+def materials(a, model, cams, pose, dev):
+    from signerf_amd.renderer import cast_rays_materials, raster_color_materials
+
+    S = a.size
+    v, f = icosphere(4)
+    vt, ft = torch.from_numpy(v).to(dev), torch.from_numpy(f).to(dev)
+    mm, vc = _bench_materials(v, f)
+    vct = torch.from_numpy(vc).to(dev)
+    world = (v.astype(np.float64) @ pose[:3, :3].T + pose[:3, 3]).astype(np.float32)
+    accel = torch.from_numpy(build_accel(world, f)).to(dev)
+    white = (1.0, 1.0, 1.0, 1.0)
+    rows = []
+    for view in range(0, 8, 2):
+        cam = cams[view]
+        bundle = cam.generate_rays(0, aabb_box=model.render_aabb)
+        o, d = bundle.origins.contiguous(), bundle.directions.contiguous()
+        host = cam._host[0].tolist()
+        fwd = (-host[2], -host[6], -host[10])
+        close = model_view(host[:12], pose).copy()
+        close[:, 3] = [0.0, 0.0, -0.27]
+        intr = (host[12], host[13], host[14], host[15], S, S)
+        for name, mv in (("bunny_5120", model_view(host[:12], pose)), ("closeup_5120", close)):
+            row = {"view": view, "mesh": name, "faces": int(f.shape[0]),
+                   "raster_depth_ms": round(timed(lambda: raster_depth(vt, ft, mv, *intr), a.reps, a.warmup), 4),
+                   "raster_color_ms": round(timed(lambda: raster_color(vt, ft, mv, *intr), a.reps, a.warmup), 4),
+                   "raster_vertex_color_ms": round(timed(lambda: raster_color(vt, ft, mv, *intr, vct, base_color=white), a.reps, a.warmup), 4),
+                   "raster_materials_ms": round(timed(lambda: raster_color_materials(vt, ft, mv, *intr, mm), a.reps, a.warmup), 4)}
+            if name == "bunny_5120":
+                row["cast_vertex_color_ms"] = round(timed(lambda: cast_rays(o, d, fwd, accel, f.shape[0], S, S, ft, vct, v.shape[0], with_color=True,
+                                                                            base_color=white), a.reps, a.warmup), 4)
+                row["cast_materials_ms"] = round(timed(lambda: cast_rays_materials(o, d, fwd, accel, f.shape[0], S, S, mm), a.reps, a.warmup), 4)
+                row["cast_materials_over_vertex_color"] = round(row["cast_materials_ms"] / row["cast_vertex_color_ms"], 3)
+            row["raster_materials_over_vertex_color"] = round(row["raster_materials_ms"] / row["raster_vertex_color_ms"], 3)
+            row["mesh_coverage"] = round(float((raster_depth(vt, ft, mv, *intr) > 0).float().mean()), 4)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    summary = {}
+    for name in ("bunny_5120", "closeup_5120"):
+        sel = [r for r in rows if r["mesh"] == name]
+        summary[name] = {k: float(np.median([r[k] for r in sel])) for k in sel[0] if k.endswith("_ms") or k.endswith("_color") or k == "mesh_coverage"}
+    out = {"size": S, "reps": a.reps, "gpu": torch.cuda.get_device_name(0), "leg": "materials", "median_over_views": summary, "rows": rows}
+    print(json.dumps({"median_over_views": summary}))
     if a.json:
         with open(a.json, "w") as fh:
             json.dump(out, fh, indent=1)
