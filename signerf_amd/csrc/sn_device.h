@@ -1156,6 +1156,28 @@ SN_DEV float sn_ordered_float(uint32_t u) {
     return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
 }
 
+// The unclamped slab test of intersect_with_aabb (signerf/utils/intersection.py:5-56): 1 / (d + 1e-6) per axis, nears = max over the
+// axes of min(lo, hi), fars = min over the axes of max(lo, hi).  The reference forms them with torch.minimum / torch.maximum / torch.max /
+// torch.min, which all hand a NaN on; fminf / fmaxf drop it and would judge such a ray by its other two axes.  A NaN comes from a
+// non-finite origin or direction component, and from 0 * inf when d == -1e-6f and the origin lies on a box plane.  So: any NaN among
+// the six plane distances makes both results NaN.  Finite inputs take the fminf / fmaxf path alone, as before.
+SN_DEV void sn_aabb_slab(const float* __restrict__ o3, const float* __restrict__ d3, const float* box, float& nears, float& fars) {
+#pragma clang fp contract(off)
+    float nr = -INFINITY, fr = INFINITY;
+    bool nan = false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float o = o3[c];
+        const float inv = 1.0f / (d3[c] + 1e-6f);
+        const float a = (box[c] - o) * inv, b = (box[3 + c] - o) * inv;
+        nan = nan || (a != a) || (b != b);
+        nr = fmaxf(nr, fminf(a, b));
+        fr = fminf(fr, fmaxf(a, b));
+    }
+    nears = nan ? __uint_as_float(0x7fc00000u) : nr;
+    fars = nan ? __uint_as_float(0x7fc00000u) : fr;
+}
+
 // ReLU as ONE integer max on the bit pattern (hipcc turns fmaxf(x, 0) on an MFMA result into TWO v_max_f32, a canonicalising
 // one first, and folds v_med3(x, 0, inf) back into the same pair): negative floats are negative ints, -0.0 is INT_MIN, positive
 // floats keep their bits.  NaN handling is restored separately where it matters (sn_main.h).

@@ -71,15 +71,8 @@ __global__ __launch_bounds__(256) void sn_mask_visible_kernel(SnMaskParams p) {
     uint32_t cnt = 0u, lo = 0xffffffffu, hi = 0u;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
 #pragma clang fp contract(off)
-        float nr = -INFINITY, fr = INFINITY;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float o = p.origins[i * 3 + c];
-            const float inv = 1.0f / (p.directions[i * 3 + c] + 1e-6f);
-            const float a = (p.aabb[c] - o) * inv, b = (p.aabb[3 + c] - o) * inv;
-            nr = fmaxf(nr, fminf(a, b));
-            fr = fminf(fr, fmaxf(a, b));
-        }
+        float nr, fr;  // NaN for a ray with a NaN plane distance: not visible, visible under inverse_mask, as in the reference
+        sn_aabb_slab(p.origins + i * 3, p.directions + i * 3, p.aabb, nr, fr);
         const float dep = p.depth[i];
         const bool non_empty = (nr < fr) && (nr > 0.0f);  // FIXME in the reference: cameras inside the box are ignored
         bool vis = (nr < dep) && (dep < fr) && non_empty;

@@ -172,16 +172,8 @@ __global__ void sn_intersect_with_aabb_kernel(const float* origins, const float*
 #pragma clang fp contract(off)
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    float nr = -INFINITY, fr = INFINITY;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float o = origins[i * 3 + c];
-        float inv = 1.0f / (directions[i * 3 + c] + 1e-6f);
-        float a = (box.v[c] - o) * inv;
-        float b = (box.v[3 + c] - o) * inv;
-        nr = fmaxf(nr, fminf(a, b));
-        fr = fminf(fr, fmaxf(a, b));
-    }
+    float nr, fr;
+    sn_aabb_slab(origins + i * 3, directions + i * 3, box.v, nr, fr);
     nears[i] = nr;
     fars[i] = fr;
 }
