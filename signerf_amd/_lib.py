@@ -18,6 +18,7 @@ SN_MESH_ABI_VERSION = 1   # include/signerf_hip_mesh.h, checked the same way
 SN_MESH_COLOR_ABI_VERSION = 1   # include/signerf_hip_mesh_color.h, checked the same way
 SN_MESH_RAYS_ABI_VERSION = 1   # include/signerf_hip_mesh_rays.h, checked the same way
 SN_MESH_MATERIAL_ABI_VERSION = 1   # include/signerf_hip_mesh_material.h, checked the same way
+SN_RAY_BATCH_ABI_VERSION = 1   # include/signerf_hip_ray_batch.h, checked the same way
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # SIGNERF_HIP_LIB: load another build of the library (A/B experiments with tools/ab_lib.sh); the default is the in-tree build
@@ -289,6 +290,14 @@ MESH_MATERIAL_SIGNATURES = {
                                               _FP, C.c_void_p]),
 }
 
+# The companion header include/signerf_hip_ray_batch.h (rays of many cameras in one launch): every symbol it declares
+# (tests/test_ray_batch_host.py checks them).
+RAY_BATCH_SIGNATURES = {
+    "sn_ray_batch_abi_version": (C.c_int, []),
+    "sn_generate_ray_batch": (C.c_int, [_FP, C.c_int32, _FP, _FP, _FP, C.c_int64, _FP, _FP, _FP, _FP, C.POINTER(C.c_float), _FP, _FP, _FP,
+                                        C.c_int32, C.c_int32, C.c_int32, _FP, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lock = threading.Lock()
 
@@ -313,7 +322,8 @@ def load() -> C.CDLL:
         except OSError as e:  # pragma: no cover
             raise SignerfHipError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in list(SIGNATURES.items()) + (list(MESH_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items())
-                                         + list(MESH_RAYS_SIGNATURES.items()) + list(MESH_MATERIAL_SIGNATURES.items())):
+                                         + list(MESH_RAYS_SIGNATURES.items()) + list(MESH_MATERIAL_SIGNATURES.items())
+                                         + list(RAY_BATCH_SIGNATURES.items())):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise SignerfHipError(f"{LIB_PATH} does not export {name}: it was built from another include/signerf_hip.h -- rebuild it "
@@ -339,6 +349,10 @@ def load() -> C.CDLL:
         if got != SN_MESH_MATERIAL_ABI_VERSION:
             raise SignerfHipError(f"{LIB_PATH} reports SN_MESH_MATERIAL_ABI_VERSION {got}, this binding was written for "
                                   f"{SN_MESH_MATERIAL_ABI_VERSION}: rebuild the library")
+        got = lib.sn_ray_batch_abi_version()
+        if got != SN_RAY_BATCH_ABI_VERSION:
+            raise SignerfHipError(f"{LIB_PATH} reports SN_RAY_BATCH_ABI_VERSION {got}, this binding was written for "
+                                  f"{SN_RAY_BATCH_ABI_VERSION}: rebuild the library")
         _lib = lib
         return lib
 

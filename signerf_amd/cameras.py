@@ -200,6 +200,7 @@ class Cameras:
         # launch without a device sync.  Built once from the constructor's arguments; indexing and .to() hand their slice of it on
         # (`_host`) instead of reading device tensors back -- cameras[i] in the sheet loops must not block the stream the previous
         # camera renders on.
+        self._tables = {}   # (device, disable_distortion) -> (device camera table, upload event): see _camera_table
         if _host is not None:
             self._host = _host
         else:
@@ -308,13 +309,19 @@ class Cameras:
         host[:, _H_W] = (host[:, _H_W].to(torch.int64) * s).to(torch.int64).float()
         host[:, _H_H] = (host[:, _H_H].to(torch.int64) * s).to(torch.int64).float()
         self._host = host
+        self._tables = {}   # the device camera tables hold the old intrinsics
 
     # -- row a5 ------------------------------------------------------------------------------------------
     def generate_rays(self, camera_indices: int = 0, coords: Optional[Tensor] = None, camera_opt_to_camera: Optional[Tensor] = None,
                       distortion_params_delta: Optional[Tensor] = None, keep_shape: Optional[bool] = None, disable_distortion: bool = False,
                       aabb_box: Optional[SceneBox] = None, obb_box: Optional[OrientedBox] = None) -> RayBundle:
-        """Ray bundle of one camera, generated on the GPU.  The signature is nerfstudio 1.0.2's [NS-RECALL, H]; an
-        argument this implementation cannot honour raises instead of being ignored.
+        """Ray bundle of one camera -- or, with a tensor ``camera_indices``, of one camera PER RAY -- generated on the GPU.
+        The signature is nerfstudio 1.0.2's [NS-RECALL, H]; an argument this implementation cannot honour raises instead of being ignored.
+
+        A tensor ``camera_indices`` [..., 1] or [...] with ``coords`` [..., 2] returns a bundle of shape [...] in ONE launch
+        (``sn_generate_ray_batch``): every ray is bit-identical to the ray ``self[c].generate_rays(0, coords=...)`` gives for its camera,
+        a camera index outside the batch gives a NaN ray, ``times`` and per-camera tensor ``metadata`` arrive gathered per ray.  A
+        one-element tensor is read as an integer (a host read-back), as before.
 
         ``camera_indices`` selects the camera of a batch (a 0-dim camera accepts only 0).  ``coords`` [..., 2] are image coordinates
         (y, x); None = every pixel centre, and the bundle is [H, W].  ``keep_shape=False`` flattens the bundle.  The camera's
@@ -324,8 +331,13 @@ class Cameras:
         """
         if isinstance(camera_indices, Tensor) and camera_indices.numel() == 1:
             camera_indices = int(camera_indices.item())
+        if isinstance(camera_indices, Tensor):
+            if coords is None:
+                raise NotImplementedError("tensor camera_indices need coords [..., 2]: the full-image bundle exists for one integer camera index")
+            return self._ray_batch(camera_indices, coords, None, camera_opt_to_camera, distortion_params_delta, keep_shape, disable_distortion,
+                                   aabb_box, obb_box)[0]
         if not isinstance(camera_indices, int):
-            raise NotImplementedError("only integer camera_indices are supported (the SIGNeRF call site passes 0)")
+            raise NotImplementedError("camera_indices must be an integer or a tensor")
         if camera_opt_to_camera is not None:
             raise NotImplementedError("camera_opt_to_camera (training-time pose refinement) is not part of the render path")
         dev = self.device
@@ -384,15 +396,8 @@ class Cameras:
                                              _lib.current_stream())
             _lib.check(st, None, "sn_generate_rays_camera")
             if aabb_box is None and obb_box is not None:
-                pose = torch.eye(4, dtype=torch.float64)
-                pose[:3, :3] = obb_box.R.detach().to("cpu", torch.float64)
-                pose[:3, 3] = obb_box.T.detach().to("cpu", torch.float64).reshape(3)
-                w2b = torch.linalg.inv(pose)[:3].to(torch.float32).reshape(-1).tolist()
-                size = obb_box.S.detach().to("cpu", torch.float32).reshape(3).tolist()
                 nears, fars = new(1), new(1)
-                st = lib.sn_intersect_obb(_lib.ptr(origins), _lib.ptr(directions), n, (C.c_float * 12)(*w2b), (C.c_float * 3)(*size),
-                                          _lib.ptr(nears), _lib.ptr(fars), _lib.current_stream())
-                _lib.check(st, None, "sn_intersect_obb")
+                self._intersect_obb(lib, obb_box, origins, directions, n, nears, fars)
         cam_idx = torch.full((*shape, 1), i % self.size, dtype=torch.int64, device=dev)
         metadata = {"directions_norm": dnorm}
         if self._metadata is not None:  # per-camera metadata rides along, broadcast over the rays [NS-RECALL, M]
@@ -402,3 +407,137 @@ class Cameras:
         times = None if self._times is None else self._times[i].reshape(*([1] * len(shape)), 1).expand(*shape, 1)
         return RayBundle(origins=origins, directions=directions, pixel_area=pixel_area, camera_indices=cam_idx,
                          nears=nears, fars=fars, metadata=metadata, times=times)
+
+    # -- rays of many cameras in one launch (include/signerf_hip_ray_batch.h) ------------------------------
+    def _host_table(self, disable_distortion: bool) -> Tensor:
+        """The SnCameraDesc records of this batch as [B, 26] int32 rows on the host (a record is 26 dwords), from the host mirror, with
+        the integer path's has_distortion rule."""
+        host = self._host
+        assert C.sizeof(_lib.SnCameraDesc) == 4 * _H_COLS
+        rec = torch.zeros((host.shape[0], _H_COLS), dtype=torch.int32)
+        rec[:, :_H_W] = host[:, :_H_W].contiguous().view(torch.int32)            # c2w, fx, fy, cx, cy: the fp32 bits
+        rec[:, 16], rec[:, 17] = host[:, _H_H].to(torch.int32), host[:, _H_W].to(torch.int32)   # the record holds height, then width
+        rec[:, 18] = host[:, _H_TYPE].to(torch.int32)
+        if not disable_distortion:
+            dist = torch.where(host[:, _H_HASDIST:_H_HASDIST + 1] != 0, host[:, _H_DIST:_H_COLS], torch.zeros(()))
+            rec[:, 19] = (dist != 0).any(dim=1).to(torch.int32)                    # all-zero parameters: the Newton steps are exactly 0
+            rec[:, _H_DIST:] = dist.contiguous().view(torch.int32)
+        return rec
+
+    def _camera_table(self, dev, disable_distortion: bool) -> Tensor:
+        """The device array of SnCameraDesc records: built from the host mirror -- no read-back --, uploaded once per (device,
+        disable_distortion) and cached; ``rescale_output_resolution`` drops the cache.  A later call on another stream waits for the
+        upload on the device, not on the host."""
+        key = (dev, bool(disable_distortion))
+        hit = self._tables.get(key)
+        if hit is None:
+            table = self._host_table(disable_distortion).to(dev)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            hit = self._tables[key] = (table, ev)
+        else:
+            torch.cuda.current_stream(dev).wait_event(hit[1])
+        return hit[0]
+
+    def generate_rays_from_indices(self, ray_indices: Tensor, images: Optional[Tensor] = None, keep_shape: Optional[bool] = None,
+                                   disable_distortion: bool = False, aabb_box: Optional[SceneBox] = None,
+                                   obb_box: Optional[OrientedBox] = None):
+        """What nerfstudio's ``RayGenerator`` computes from a pixel sampler's ``ray_indices`` [..., 3] = (camera, y, x) -- the rays through
+        the pixel centres ``image_coords[y, x]`` -- in one launch, and in the SAME launch the target pixels of a uint8 image stack
+        ``images`` [B, H, W, C] on the cameras' device: ``images[c, y, x].float() / 255`` to the bit, NaN for a (y, x) outside the stack.
+        Returns (RayBundle, pixels [..., C] | None)."""
+        return self._ray_batch(None, None, ray_indices, keep_shape=keep_shape, disable_distortion=disable_distortion, aabb_box=aabb_box,
+                               obb_box=obb_box, images=images)
+
+    def _ray_batch(self, camera_indices: Optional[Tensor], coords: Optional[Tensor], ray_indices: Optional[Tensor],
+                   camera_opt_to_camera=None, distortion_params_delta=None, keep_shape: Optional[bool] = None,
+                   disable_distortion: bool = False, aabb_box: Optional[SceneBox] = None, obb_box: Optional[OrientedBox] = None,
+                   images: Optional[Tensor] = None):
+        """``generate_rays`` with a camera per ray: (``camera_indices`` [..., 1] | [...], ``coords`` [..., 2]) or ``ray_indices`` [..., 3]
+        (camera, y, x: the pixel centres), and with the latter optionally the pixels of a uint8 stack ``images`` [B, H, W, C].
+        Returns (RayBundle of shape [...], pixels [..., C] | None).  The argument checks read the host mirror and come before the
+        GPU is touched; nothing here waits for the device."""
+        if camera_opt_to_camera is not None:
+            raise NotImplementedError("camera_opt_to_camera (training-time pose refinement) is not part of the render path")
+        if distortion_params_delta is not None:
+            raise NotImplementedError("distortion_params_delta is per camera: it is not supported with tensor camera_indices")
+        types = self._host[:, _H_TYPE].to(torch.int64).tolist()
+        bad = sorted({t for t in types if t not in _SUPPORTED_TYPES})
+        if bad:
+            names = [CameraType(t).name if t in [x.value for x in CameraType] else str(t) for t in bad]
+            raise NotImplementedError(f"camera_type {', '.join(names)} is not supported by the HIP ray generation (PERSPECTIVE, FISHEYE and "
+                                      "EQUIRECTANGULAR are): a ray batch may draw from every camera of the batch")
+        if ray_indices is not None:
+            if ray_indices.shape[-1] != 3:
+                raise ValueError("ray_indices must be [..., 3]: (camera, y, x)")
+            shape = tuple(ray_indices.shape[:-1])
+        else:
+            if coords.shape[-1] != 2:
+                raise ValueError("coords must be [..., 2] image coordinates (y, x)")
+            shape = tuple(coords.shape[:-1])
+            if tuple(camera_indices.shape) != shape:
+                if camera_indices.shape[-1:] != (1,) or tuple(camera_indices.shape[:-1]) != shape:
+                    raise ValueError(f"camera_indices {tuple(camera_indices.shape)} must be [..., 1] or [...] for coords {tuple(coords.shape)}")
+        dev = self.device
+        if dev.type != "cuda":
+            raise _lib.SignerfHipError("Cameras.generate_rays needs the cameras on the GPU: call .to('cuda') first")
+        if images is not None:
+            if ray_indices is None:
+                raise ValueError("pixels are gathered with ray_indices [..., 3] only")
+            if images.dtype != torch.uint8 or images.ndim != 4 or images.shape[0] != self.size or not 1 <= images.shape[3] <= 4:
+                raise ValueError(f"images must be a uint8 stack [{self.size}, H, W, C] with C in 1..4, one image per camera")
+            if images.device != dev:
+                raise _lib.SignerfHipError("the image stack must live on the cameras' device")
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            ridx = cidx = cflat = None
+            if ray_indices is not None:
+                ridx = ray_indices.to(device=dev, dtype=torch.int64).reshape(-1, 3).contiguous()
+                cidx, n = ridx[:, 0], ridx.shape[0]
+            else:
+                cidx = camera_indices.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+                cflat = coords.to(device=dev, dtype=torch.float32).reshape(-1, 2).contiguous()
+                n = cidx.shape[0]
+            if keep_shape is False:
+                shape = (n,)
+            new = lambda c: torch.empty((*shape, c), dtype=torch.float32, device=dev)  # noqa: E731
+            origins, directions, pixel_area, dnorm = new(3), new(3), new(1), new(1)
+            box = aabb_box is not None or obb_box is not None
+            nears, fars = (new(1), new(1)) if box else (None, None)
+            pixels = None if images is None else new(images.shape[3])
+            if n > 0:   # (an empty tensor has a NULL data pointer)
+                aabb_arr = None
+                if aabb_box is not None:
+                    aabb_arr = (C.c_float * 6)(*aabb_box.aabb.detach().to("cpu", torch.float32).reshape(-1).tolist())
+                table = self._camera_table(dev, disable_distortion)
+                img = None if images is None else images.contiguous()
+                ih, iw, ic = (0, 0, 0) if img is None else img.shape[1:]
+                st = lib.sn_generate_ray_batch(_lib.ptr(table), self.size, _lib.ptr(ridx), None if ridx is not None else _lib.ptr(cidx),
+                                               _lib.ptr(cflat), n, _lib.ptr(origins), _lib.ptr(directions), _lib.ptr(pixel_area),
+                                               _lib.ptr(dnorm), aabb_arr, _lib.ptr(nears) if aabb_arr is not None else None,
+                                               _lib.ptr(fars) if aabb_arr is not None else None, _lib.ptr(img), ih, iw, ic, _lib.ptr(pixels),
+                                               _lib.current_stream())
+                _lib.check(st, None, "sn_generate_ray_batch")
+                if aabb_box is None and obb_box is not None:
+                    self._intersect_obb(lib, obb_box, origins, directions, n, nears, fars)
+        safe = cidx.clamp(0, self.size - 1)   # the gathers below must not read outside the batch either
+        metadata = {"directions_norm": dnorm}
+        if self._metadata is not None:
+            for k, v in self._metadata.items():
+                if isinstance(v, Tensor) and v.ndim > 0 and v.shape[0] == self.size:
+                    metadata[k] = v.to(dev).reshape(self.size, -1)[safe].reshape(*shape, -1)
+        times = None if self._times is None else self._times[safe].reshape(*shape, 1)
+        bundle = RayBundle(origins=origins, directions=directions, pixel_area=pixel_area, camera_indices=cidx.reshape(*shape, 1),
+                           nears=nears, fars=fars, metadata=metadata, times=times)
+        return bundle, pixels
+
+    @staticmethod
+    def _intersect_obb(lib, obb_box: OrientedBox, origins: Tensor, directions: Tensor, n: int, nears: Tensor, fars: Tensor) -> None:
+        pose = torch.eye(4, dtype=torch.float64)
+        pose[:3, :3] = obb_box.R.detach().to("cpu", torch.float64)
+        pose[:3, 3] = obb_box.T.detach().to("cpu", torch.float64).reshape(3)
+        w2b = torch.linalg.inv(pose)[:3].to(torch.float32).reshape(-1).tolist()
+        size = obb_box.S.detach().to("cpu", torch.float32).reshape(3).tolist()
+        st = lib.sn_intersect_obb(_lib.ptr(origins), _lib.ptr(directions), n, (C.c_float * 12)(*w2b), (C.c_float * 3)(*size),
+                                  _lib.ptr(nears), _lib.ptr(fars), _lib.current_stream())
+        _lib.check(st, None, "sn_intersect_obb")

@@ -5,6 +5,7 @@
 #include "../../include/signerf_hip_mesh_color.h"
 #include "../../include/signerf_hip_mesh_rays.h"
 #include "../../include/signerf_hip_mesh_material.h"
+#include "../../include/signerf_hip_ray_batch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -30,6 +31,7 @@
 #include "sn_normals.h"
 #include "sn_proposal.h"
 #include "sn_stage.h"
+#include "sn_ray_batch.h"
 
 namespace {
 
@@ -2632,6 +2634,52 @@ int sn_mesh_cast_rays_materials(const float* origins, const float* directions, i
     return end_launches(who);
 }
 
+
+// ---- include/signerf_hip_ray_batch.h: rays of many cameras in one launch ---------------------------------------------------------------
+int sn_ray_batch_abi_version(void) { return SN_RAY_BATCH_ABI_VERSION; }
+
+int sn_generate_ray_batch(const SnCameraDesc* cameras, int32_t n_cameras, const int64_t* ray_indices, const int64_t* camera_indices,
+                          const float* coords, int64_t n, float* origins, float* directions, float* pixel_area, float* directions_norm,
+                          const float* aabb, float* nears, float* fars, const uint8_t* images, int32_t img_h, int32_t img_w,
+                          int32_t img_c, float* pixels, SnStream stream) {
+    const std::string who = "sn_generate_ray_batch";
+    if (!cameras || n_cameras < 1 || n < 0) return fail(nullptr, SN_ERR_INVALID, who + ": bad argument (cameras, n_cameras >= 1, n >= 0)");
+    const bool triplets = ray_indices != nullptr, pairs = camera_indices != nullptr || coords != nullptr;
+    if (triplets == pairs)
+        return fail(nullptr, SN_ERR_INVALID, who + ": give exactly one index form, ray_indices [n,3] or camera_indices [n] with coords [n,2]");
+    if (pairs && (!camera_indices || !coords)) return fail(nullptr, SN_ERR_INVALID, who + ": camera_indices and coords go together");
+    if ((images != nullptr) != (pixels != nullptr)) return fail(nullptr, SN_ERR_INVALID, who + ": images and pixels go together");
+    if (images) {
+        if (!triplets) return fail(nullptr, SN_ERR_INVALID, who + ": pixels are gathered with the ray_indices form only");
+        if (img_h < 1 || img_w < 1 || img_c < 1 || img_c > 4)
+            return fail(nullptr, SN_ERR_INVALID, who + ": the image stack needs img_h, img_w >= 1 and img_c in 1..4");
+    }
+    if (n == 0) return SN_OK;
+    SnRayBatchParams p;
+    memset(&p, 0, sizeof(p));
+    p.cameras = cameras;
+    p.n_cameras = n_cameras;
+    p.ray_indices = ray_indices;
+    p.camera_indices = camera_indices;
+    p.coords = coords;
+    p.n = n;
+    p.origins = origins;
+    p.directions = directions;
+    p.pixel_area = pixel_area;
+    p.directions_norm = directions_norm;
+    p.has_aabb = aabb != nullptr;
+    if (aabb) memcpy(p.aabb, aabb, sizeof(p.aabb));
+    p.nears = nears;
+    p.fars = fars;
+    p.images = images;
+    p.img_h = img_h;
+    p.img_w = img_w;
+    p.img_c = img_c;
+    p.pixels = pixels;
+    if ((n + 255) / 256 > 0x7fffffffll) return fail(nullptr, SN_ERR_INVALID, who + ": n exceeds the grid (2^31 - 1 blocks of 256 rays)");
+    hipLaunchKernelGGL(sn_ray_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
+    return end_launches(who);
+}
 
 int sn_tensor_to_uint8(const float* in, int64_t n, uint8_t* out, SnStream stream) {
     if (!in || !out || n < 0) return fail(nullptr, SN_ERR_INVALID, "sn_tensor_to_uint8: bad argument");

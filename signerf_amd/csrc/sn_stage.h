@@ -90,6 +90,83 @@ SN_DEV void sn_cam_dir(const float* c2w, float u, float v, float out[3], float& 
     norm = n;
 }
 
+// One ray of one camera from its image coordinates (y, x): what sn_generate_rays_kernel computes per pixel and sn_ray_batch_kernel
+// (sn_ray_batch.h) per (camera, y, x) triplet -- the ONE copy of this arithmetic, so the two kernels agree to the bit.  `area` is
+// computed with want_area, `tnear` / `tfar` with want_box (nerfstudio intersect_aabb: clamped slab test, invalid -> 1e10, A1).
+struct SnRay {
+    float o[3], d[3];
+    float area, norm, tnear, tfar;
+};
+
+template <int TYPE, bool DISTORT>
+SN_DEV void sn_camera_ray(const float* c2w, float fx, float fy, float cx, float cy, const float* dist, float x, float y, bool want_area,
+                          bool want_box, const float* aabb, SnRay& r) {
+#pragma clang fp contract(off)
+    float u = (x - cx) / fx, v = -((y - cy) / fy);
+    float ux = (x - cx + 1.0f) / fx, vx = v;
+    float uy = u, vy = -((y - cy + 1.0f) / fy);
+    if (DISTORT) {
+        const float u0 = u, v0 = v;
+        sn_undistort(dist, u0, v0, u, v);
+        sn_undistort(dist, ux, v0, ux, vx);
+        sn_undistort(dist, u0, vy, uy, vy);
+    }
+    float dx[3], dy[3], n1, n2;
+    sn_cam_dir<TYPE>(c2w, u, v, r.d, r.norm);
+    sn_cam_dir<TYPE>(c2w, ux, vx, dx, n1);
+    sn_cam_dir<TYPE>(c2w, uy, vy, dy, n2);
+    r.o[0] = c2w[3];
+    r.o[1] = c2w[7];
+    r.o[2] = c2w[11];
+    if (want_area) {
+        float a = 0.f, b = 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float e = r.d[c] - dx[c], f = r.d[c] - dy[c];
+            a = c == 0 ? e * e : a + e * e;
+            b = c == 0 ? f * f : b + f * f;
+        }
+        r.area = sqrtf(a) * sqrtf(b);
+    }
+    if (want_box) {
+        float tmin = -INFINITY, tmax = INFINITY;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float a = (aabb[c] - r.o[c]) / r.d[c];
+            float b = (aabb[3 + c] - r.o[c]) / r.d[c];
+            tmin = fmaxf(tmin, fminf(a, b));
+            tmax = fminf(tmax, fmaxf(a, b));
+        }
+        tmin = fminf(fmaxf(tmin, 0.0f), 1e10f);
+        tmax = fminf(fmaxf(tmax, 0.0f), 1e10f);
+        if (tmax <= tmin) {
+            tmin = 1e10f;
+            tmax = 1e10f;
+        }
+        r.tnear = tmin;
+        r.tfar = tmax;
+    }
+}
+
+// the stores of one ray (row i of every output that is not NULL)
+SN_DEV void sn_store_ray(const SnRay& r, int64_t i, float* origins, float* directions, float* pixel_area, float* directions_norm, float* nears,
+                         float* fars) {
+    if (origins) {
+        origins[i * 3 + 0] = r.o[0];
+        origins[i * 3 + 1] = r.o[1];
+        origins[i * 3 + 2] = r.o[2];
+    }
+    if (directions) {
+        directions[i * 3 + 0] = r.d[0];
+        directions[i * 3 + 1] = r.d[1];
+        directions[i * 3 + 2] = r.d[2];
+    }
+    if (pixel_area) pixel_area[i] = r.area;
+    if (directions_norm) directions_norm[i] = r.norm;
+    if (nears) nears[i] = r.tnear;
+    if (fars) fars[i] = r.tfar;
+}
+
 template <int TYPE, bool DISTORT>
 __global__ void sn_generate_rays_kernel(SnRayGenParams p) {
 #pragma clang fp contract(off)
@@ -104,60 +181,10 @@ __global__ void sn_generate_rays_kernel(SnRayGenParams p) {
         x = (float)ix + 0.5f;
         y = (float)iy + 0.5f;
     }
-    float u = (x - p.cx) / p.fx, v = -((y - p.cy) / p.fy);
-    float ux = (x - p.cx + 1.0f) / p.fx, vx = v;
-    float uy = u, vy = -((y - p.cy + 1.0f) / p.fy);
-    if (DISTORT) {
-        const float u0 = u, v0 = v;
-        sn_undistort(p.dist, u0, v0, u, v);
-        sn_undistort(p.dist, ux, v0, ux, vx);
-        sn_undistort(p.dist, u0, vy, uy, vy);
-    }
-    float d[3], dx[3], dy[3], nrm, n1, n2;
-    sn_cam_dir<TYPE>(p.c2w, u, v, d, nrm);
-    sn_cam_dir<TYPE>(p.c2w, ux, vx, dx, n1);
-    sn_cam_dir<TYPE>(p.c2w, uy, vy, dy, n2);
-    float o[3] = {p.c2w[3], p.c2w[7], p.c2w[11]};
-    if (p.origins) {
-        p.origins[i * 3 + 0] = o[0];
-        p.origins[i * 3 + 1] = o[1];
-        p.origins[i * 3 + 2] = o[2];
-    }
-    if (p.directions) {
-        p.directions[i * 3 + 0] = d[0];
-        p.directions[i * 3 + 1] = d[1];
-        p.directions[i * 3 + 2] = d[2];
-    }
-    if (p.pixel_area) {
-        float a = 0.f, b = 0.f;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float e = d[c] - dx[c], f = d[c] - dy[c];
-            a = c == 0 ? e * e : a + e * e;
-            b = c == 0 ? f * f : b + f * f;
-        }
-        p.pixel_area[i] = sqrtf(a) * sqrtf(b);
-    }
-    if (p.directions_norm) p.directions_norm[i] = nrm;
-    if (p.has_aabb && p.nears && p.fars) {
-        // nerfstudio intersect_aabb: clamped slab test, invalid -> 1e10 (A1)
-        float tmin = -INFINITY, tmax = INFINITY;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float a = (p.aabb[c] - o[c]) / d[c];
-            float b = (p.aabb[3 + c] - o[c]) / d[c];
-            tmin = fmaxf(tmin, fminf(a, b));
-            tmax = fminf(tmax, fmaxf(a, b));
-        }
-        tmin = fminf(fmaxf(tmin, 0.0f), 1e10f);
-        tmax = fminf(fmaxf(tmax, 0.0f), 1e10f);
-        if (tmax <= tmin) {
-            tmin = 1e10f;
-            tmax = 1e10f;
-        }
-        p.nears[i] = tmin;
-        p.fars[i] = tmax;
-    }
+    const bool box = p.has_aabb && p.nears && p.fars;
+    SnRay r;
+    sn_camera_ray<TYPE, DISTORT>(p.c2w, p.fx, p.fy, p.cx, p.cy, p.dist, x, y, p.pixel_area != nullptr, box, p.aabb, r);
+    sn_store_ray(r, i, p.origins, p.directions, p.pixel_area, p.directions_norm, box ? p.nears : nullptr, box ? p.fars : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------

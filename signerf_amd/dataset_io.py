@@ -67,6 +67,22 @@ def load_previous_experiment_cameras(transforms_path: Union[str, Path]) -> Tuple
     return reference, synthetic, bool(transforms.get("is_combined", False))
 
 
+def load_generated_frames(transforms_path: Union[str, Path]) -> Dict[str, Any]:
+    """The frames of a transforms.json that ``GeneratedDataset.save_generated_images`` wrote, as the columns a ``Cameras`` is built from:
+    ``camera_to_worlds`` [N,3,4] (the frames' ``transform_matrix``: scene space), ``fx, fy, cx, cy`` fp32 [N], ``width, height`` int64
+    [N] and ``file_paths`` (absolute, the frames' ``file_path`` resolved against the file's directory)."""
+    transforms_path = Path(transforms_path)
+    with open(transforms_path) as f:
+        frames = json.load(f)["frames"]
+    if not frames:
+        raise ValueError(f"{transforms_path} holds no frames")
+    col = lambda key, dt: torch.tensor([fr[key] for fr in frames], dtype=dt)  # noqa: E731
+    return {"camera_to_worlds": torch.stack([torch.tensor(fr["transform_matrix"], dtype=torch.float32)[:3] for fr in frames], dim=0),
+            "fx": col("fl_x", torch.float32), "fy": col("fl_y", torch.float32), "cx": col("cx", torch.float32),
+            "cy": col("cy", torch.float32), "width": col("w", torch.int64), "height": col("h", torch.int64),
+            "file_paths": [transforms_path.parent / fr["file_path"] for fr in frames]}
+
+
 def encode_png(u8, compress_level: int = 6) -> bytes:
     """A PNG file of an 8-bit [H,W,1] (greyscale) or [H,W,3] (RGB) array -- the same pixels `PIL.Image.save` writes, encoded WITHOUT the
     interpreter lock: numpy forms the filtered scanlines (filter "Up": each row minus the row above, row 0 unfiltered) and `zlib.compress`
