@@ -382,7 +382,9 @@ typedef struct SnDebugLayout {
 } SnDebugLayout;
 /* which: -1 main field, i >= 0 proposal net i. */
 int sn_debug_layout(SnHandle h, int32_t which, SnDebugLayout* out);
-/* what: 0 = the buffer of de-hashed copies, 1 = the x-paired tables (proposal nets).  dst: device pointer, bytes must match. */
+/* what: 0 = the buffer of de-hashed copies, 1 = the x-paired tables (proposal nets); the weight images sn_finalize_weights packed on the
+ * host, whatever `which` is: 2 = the exact-fp32 main image, 3 = its split-precision form (with the single-fp16 tail), 4 = the normals image,
+ * 5 = its split-precision form; 6 = the MLP pack of proposal net `which` (needs which >= 0).  dst: device pointer, bytes must match. */
 int sn_debug_read(SnHandle h, int32_t which, int32_t what, void* dst, size_t bytes, SnStream stream);
 /* The switches of the environment ("Conventions") are read by sn_create and sn_finalize_weights, never by a render call; a test that flips one between two renders
  * of the same handle calls this to have it re-read. */

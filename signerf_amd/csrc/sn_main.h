@@ -20,23 +20,10 @@
 //   A "k-slot" (t, h) of a layer = k-step t, lane half h.  rho(r) = (r&3)+8*(r>>2).
 #pragma once
 #include "sn_device.h"
+#include "sn_layout.h"
 
-// LDS weight image of the main field, float offsets.  Built on the host by sn_api.hip
-// (build_main_image) -- keep the two in sync.
-struct SnMainImg {
-    static constexpr int W1 = 0;        // [rt=2][t4=4][lane=64][4]   32 -> 64
-    static constexpr int W2 = 2048;     // [rt=1][t4=8][64][4]        64 -> 32 rows (16 real + dup)
-    static constexpr int WC1 = 4096;    // [rt=2][t4=4][64][4]        (16 L2-rows + 16 SH) -> 64
-    static constexpr int WC2 = 6144;    // [rt=2][t4=8][64][4]        64 -> 64
-    static constexpr int B1 = 10240;    // [rt=2][h=2][16]
-    static constexpr int B2 = 10304;    // [1][2][16]
-    static constexpr int BC1 = 10336;   // [2][2][16]
-    static constexpr int BC2 = 10400;   // [2][2][16]
-    static constexpr int W3 = 10464;    // [n][h=2][32], n = 3 channels
-    static constexpr int W3_ROWS = 3;
-    static constexpr int B3 = W3 + W3_ROWS * 64;  // [4]: the 3 biases; [3] = 1 / (output scale of layer 2) of the split-precision image (h0 = row 0 * that)
-    static constexpr int TOTAL = B3 + 4;  // 10 660 floats = 42 640 bytes; a multiple of 4
-};
+// The LDS weight images (SnMainImg, SnMainImgH, SnMainImgF16) are laid out in sn_layout.h and built on the host by sn_weights.h
+// (build_main_image, build_main_image_h, pack_main_images) -- keep the two in sync.
 
 // acc[rt] (tile 0) / acc[rt] (tile 1) <- bias + W . op     (exact fp32 MFMA)
 template <int RT, int KS>
@@ -183,19 +170,6 @@ SN_DEV void sn_main_field_f32(const float* __restrict__ lds, float* feat, const 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-// byte offsets of the fp16x2 LDS image; weights [rt][s][hi|lo][lane][8 halves]
-struct SnMainImgH {
-    static constexpr int W1 = 0;          // 2 rt x 2 s x 2 x 1 KiB
-    static constexpr int W2 = 8192;       // 1 x 4 x 2 KiB
-    static constexpr int WC1 = 16384;     // 2 x 2 x 2 KiB
-    static constexpr int WC2 = 24576;     // 2 x 4 x 2 KiB
-    static constexpr int FP32 = 40960;    // then the fp32 tail, same sub-layout as SnMainImg from B1 on
-    static constexpr int TAIL_FLOATS = SnMainImg::TOTAL - SnMainImg::B1;
-    static constexpr int TOTAL_BYTES = FP32 + TAIL_FLOATS * 4;  // 42640
-    static constexpr int B1 = 0, B2 = SnMainImg::B2 - SnMainImg::B1, BC1 = SnMainImg::BC1 - SnMainImg::B1,
-                         BC2 = SnMainImg::BC2 - SnMainImg::B1, W3 = SnMainImg::W3 - SnMainImg::B1, B3 = SnMainImg::B3 - SnMainImg::B1;
-};
-
 // two fp32 -> packed fp16 hi pair and lo pair: hi = RTZ(a), lo = RTZ(a - hi).  The difference is formed by v_fma_mix_f32, which
 // reads the fp16 half straight out of the packed register (fma(hi16, -1.0, a) in fp32, exact) -- 4 instructions per pair
 // instead of mask, mask, convert, packed subtract, convert.  hipcc does not select fma_mix for this pattern, hence the asm
@@ -221,9 +195,6 @@ SN_DEV void sn_split2(float a, float b, uint32_t& hi, uint32_t& lo) {
 // stays below 1 because |a| < 2048 -- the clamp of v_fma_mix_f32 is then exactly max(., 0).  5 instructions per pair instead of 6
 // (two v_max_i32 + the plain split): -128 VALU per wave-step.  (r01 had tried the same fold without the range guarantee and dropped it:
 // activations >= 2048 lose their low part.)
-#ifndef SN_RELU_FOLD
-#define SN_RELU_FOLD 1
-#endif
 SN_DEV void sn_split2_relu(float a, float b, uint32_t& hi, uint32_t& lo) {
     const uint32_t hr = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(a, b));
     float la, lb;
@@ -467,13 +438,6 @@ SN_DEV void sn_main_field_h(const char* __restrict__ ldsb, float* feat, const Sn
 // behind the image (SnMainImgF16).  48 MFMAs and ~220 conversion VALU per wave-step instead of 120 and ~670.
 // oracle/tcnn_layout.py emulates exactly these roundings; what is NOT reproduced is the library's fp16 ACCUMULATION inside a layer.
 // ==========================================================================================
-struct SnMainImgF16 {
-    static constexpr int W3H = SnMainImg::TOTAL * 4;   // byte offset: A operand of colour layer 3, [s = 4][lane = 64][8 halves], rows 0..2 real
-    static constexpr int TAILF = W3H + 4096;           // float[4]: [0] = 1 / s5 (the power-of-two scale of that operand)
-    static constexpr int TOTAL_BYTES = TAILF + 16;
-    static constexpr int TOTAL_FLOATS = TOTAL_BYTES / 4;
-};
-
 // RNE (v_cvt_pkrtz_f16_f32 truncates): hipcc selects v_cvt_pk_f16_f32 for the vector conversion.  NOT inline asm: its operands are MFMA
 // results, and the compiler inserts the wait states an MFMA write -> VALU read needs only in front of instructions it knows (found on
 // hardware, r04: with an asm conversion the geometry rows came back as garbage that changed with unrelated code further down).

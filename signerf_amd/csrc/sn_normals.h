@@ -19,19 +19,8 @@
 //      through the SAME image slots and code path as the colour MLP, with the position encoding in the SH slots and its last
 //      two linear layers (64 -> 64, no activation, then the 64 -> 3 head) multiplied together on the host.
 #pragma once
+#include "sn_layout.h"  // SnNormImg, SnNormImgH
 #include "sn_main.h"
-
-struct SnNormImg {  // float offsets.  [0, SnMainImg::TOTAL) has SnMainImg's layout, the pred-normal MLP in the colour slots
-    static constexpr int WB = SnMainImg::TOTAL;  // [rt=1][t4=8][64][4]: mask (64, layer-1 output order) -> d h0 / d feat (32 rows)
-    static constexpr int ZB = WB + 2048;         // its bias image: 32 zeros
-    static constexpr int TOTAL = ZB + 32;        // 12 740 floats = 50 960 B
-};
-
-// fp16x2 form: SnMainImgH (pred-normal MLP in the colour slots) followed by the reverse-pass layer in the same operand order
-struct SnNormImgH {
-    static constexpr int WB = SnMainImgH::TOTAL_BYTES;  // [s=4][hi|lo][lane][8 halves] = 8 KiB
-    static constexpr int TOTAL_BYTES = WB + 8192;       // 50 832
-};
 
 struct SnNormalsParams {
     const float* origins;

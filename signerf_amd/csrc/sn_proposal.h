@@ -18,6 +18,7 @@
 #pragma once
 #include "../../include/signerf_hip.h"
 #include "sn_device.h"
+#include "sn_layout.h"  // the proposal-net MLP pack: SN_PROP_W0 .. SN_PROP_PACK_FLOATS
 #include "sn_main.h"  // fp16 hi+lo split helpers (sn_split2, f16x8)
 
 #define SN_PROP_MAX_SAMPLES 256
@@ -32,24 +33,6 @@
 #ifndef SN_PROP_CACHE
 #define SN_PROP_CACHE 4
 #endif
-
-// proposal-net MLP pack (floats): W0 [k=10][n=16] (k-major), b0 [16], W1 [16], b1
-#define SN_PROP_W0 0
-#define SN_PROP_B0 160
-#define SN_PROP_W1 176
-#define SN_PROP_B1 192
-// ... followed by the matrix-core form of the same weights (SN_PROP_MFMA): two A operands of v_mfma_f32_32x32x16_f16 as fp16 hi / lo
-// parts, [lane][8 halves] each (sn_prop_mlp_mfma below: rows 0..15 serve the rays of lanes 0..31 through k = 0..7, rows 16..31 the rays
-// of lanes 32..63 through k = 8..15), and the layer-2 weights in accumulator order, [h][r] = W1[(r & 3) + 8 (r >> 2) + 4 h], r = 0..7
-#define SN_PROP_MA1_HI 196
-#define SN_PROP_MA1_LO 452
-#define SN_PROP_MA2_HI 708
-#define SN_PROP_MA2_LO 964
-#define SN_PROP_MW1 1220
-// ... and the linear half of layer 2 (sn_prop_mlp_mfma): [k < 10] = sum_r W1[r] W0[r][k] / 2 (per unit of the SCALED features), [10] =
-// sum_r W1[r] b0[r] / 2 + b1
-#define SN_PROP_LIN 1236
-#define SN_PROP_PACK_FLOATS 1252
 
 struct SnScal5 {
     float v[5];
