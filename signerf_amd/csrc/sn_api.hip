@@ -32,6 +32,7 @@
 #include "sn_proposal.h"
 #include "sn_stage.h"
 #include "sn_ray_batch.h"
+#include "sn_variant.h"
 #include "sn_weights.h"
 
 namespace {
@@ -110,6 +111,8 @@ struct SnContext {
 #ifndef SN_DENSE_LEVELS_DEFAULT
 #define SN_DENSE_LEVELS_DEFAULT 11
 #endif
+static_assert(kSnDenseLevelsDefault == SN_DENSE_LEVELS_DEFAULT && kSnBcMain == SN_BC_MAIN && kSnPropMaxSamples == SN_PROP_MAX_SAMPLES,
+              "sn_variant.h selects among the instantiations these constants name");
 
 namespace {
 
@@ -351,17 +354,11 @@ bool check_hashmlp(const SnHashMlpDesc& d, int levels, int hidden, int out, std:
     return false;
 }
 
-// tiny-cuda-nn level table (grid_mode 1): resolution = ceil(scale) + 1; a level is dense when its whole grid fits the table
+// tiny-cuda-nn level table (grid_mode 1; sn_variant.h sn_tcnn_dense_res), packed as the kernels take it
 SnGridLevels grid_levels(const SnHashMlpDesc& d) {
     SnGridLevels g;
     memset(&g, 0, sizeof(g));
-    if (d.grid_mode != 1) return g;
-    const uint64_t T = 1ull << d.log2_hashmap_size;
-    for (int l = 0; l < d.num_levels; ++l) {
-        const uint64_t res = (uint64_t)ceilf(d.scalings[l]) + 1;
-        const uint64_t n = res * res * res;
-        if (n <= T && res <= 255) g.packed[l >> 2] |= (uint32_t)res << ((l & 3) * 8);
-    }
+    for (int l = 0; l < d.num_levels; ++l) g.packed[l >> 2] |= sn_tcnn_dense_res(d, l) << ((l & 3) * 8);
     return g;
 }
 
@@ -508,20 +505,6 @@ int build_half_grid(SnHandle h, const SnHashMlpDesc& d, const DevBuf& table, con
 #endif
     SN_HIP(h, hipGetLastError());
     return SN_OK;
-}
-
-// number of leading dense levels if the dense levels form a prefix of the level list, else -1
-int leading_dense(const SnHashMlpDesc& d) {
-    const SnGridLevels g = grid_levels(d);
-    int nd = 0;
-    bool ended = false;
-    for (int l = 0; l < d.num_levels; ++l) {
-        const bool dense = ((g.packed[l >> 2] >> ((l & 3) * 8)) & 0xffu) != 0u;
-        if (dense && ended) return -1;
-        if (dense) ++nd;
-        else ended = true;
-    }
-    return nd;
 }
 
 const std::vector<float>* find(SnHandle h, const std::string& name, size_t count) {
@@ -705,32 +688,64 @@ WorkspacePlan plan_workspace(int height, int width, const SnRenderOpts& o, int n
     return w;
 }
 
-// The non-default sampler / position map run in the ALT instantiations of K1 / K2 / K3 (run-time-generic: uploaded tables, no de-hashed
-// copies, STRICT position arithmetic), so that the production kernels' code does not depend on them.  A far plane beyond 1e7 goes there
-// too: out there the exact contraction rounds onto the face q = 1 (dropped by the selector) and the production kernels' reciprocal
-// form may not (sn_sample_q_fast).
-bool needs_generic_kernels(SnHandle h, const SnRenderOpts* opts) {
-    return opts->spacing_mode != 0 || h->pos_map.box != 0 || !(opts->far_plane <= 1.0e7f);
+// ---- launch selection (sn_variant.h) --------------------------------------------------------------------------------------------------
+// what selection depends on: the finalized handle's side ...
+SnVariantFacts variant_facts(SnHandle h) {
+    const SnFieldDesc& d = h->desc;
+    SnVariantFacts f{};
+    f.main_grid_mode = d.main_field.grid_mode;
+    f.prop_grid_mode = d.num_proposals > 0 ? d.proposals[0].grid_mode : 0;
+    f.nd_torch = h->nd_torch;
+    f.td_main = leading_dense(d.main_field);
+    for (int i = 0; i < d.num_proposals; ++i) {
+        f.nd_prop[i] = h->nd_prop[i];
+        f.td_prop[i] = leading_dense(d.proposals[i]);
+    }
+    f.split_ok = h->split_ok;
+    f.normals_split_ok = h->normals_split_ok;
+    f.has_half_grid = h->hquads_main.ptr && h->hrows_main.ptr;
+    f.has_dense_main = h->dense_main.ptr != nullptr;
+    f.box = h->pos_map.box;
+    f.num_proposals = d.num_proposals;
+    return f;
+}
+// ... and the call's
+SnVariantRequest variant_request(const SnRenderOpts& o, bool dump) {
+    return SnVariantRequest{o.num_proposal_iterations, o.precision, o.spacing_mode, o.far_plane, dump, o.march_stats != nullptr};
 }
 
-bool valid_opts(const SnFieldDesc& d, const SnRenderOpts& o, std::string& why) {
-    if (o.num_proposal_iterations < 0 || o.num_proposal_iterations > d.num_proposals) why = "num_proposal_iterations exceeds the proposal nets of this handle";
-    else if (o.num_nerf_samples < 1 || o.num_nerf_samples > 1024) why = "num_nerf_samples out of range [1,1024]";
-    else if (o.chunk_rays < 1) why = "chunk_rays must be positive";
-    else if (o.precision < 0 || o.precision > 2) why = "precision must be 0 (fp32), 1 (split fp16) or 2 (single fp16, tiny-cuda-nn grids)";
-    else if (o.precision == 2 && d.main_field.grid_mode != 1)
-        why = "precision 2 (single fp16) is the arithmetic of tiny-cuda-nn checkpoints: it needs main_field.grid_mode = 1";
-    else if (o.background_mode != 0 && o.background_mode != 1) why = "background_mode must be 0 (last sample) or 1 (constant colour)";
-    else if (o.spacing_mode != 0 && o.spacing_mode != 1) why = "spacing_mode must be 0 (piecewise) or 1 (uniform)";
-    else {
-        for (int i = 0; i < o.num_proposal_iterations; ++i)
-            if (o.num_proposal_samples[i] < 2 || o.num_proposal_samples[i] > SN_PROP_MAX_SAMPLES) {
-                why = "num_proposal_samples out of range [2," + std::to_string(SN_PROP_MAX_SAMPLES) + "]";
-                return false;
-            }
-        return true;
-    }
-    return false;
+// tuple -> kernel, generated from the lists of sn_variant.h: these tables are what instantiates the three kernels
+template <typename V, typename P>
+struct KernelEntry {
+    V v;
+    void (*fn)(P);
+};
+#define SN_X(...) {{__VA_ARGS__}, &sn_render_main_kernel<__VA_ARGS__>},
+const KernelEntry<SnMainVariant, SnMainParams> kMainKernels[] = {SN_MAIN_VARIANTS(SN_X)};
+#undef SN_X
+#define SN_X(...) {{__VA_ARGS__}, &sn_proposal_kernel<__VA_ARGS__>},
+const KernelEntry<SnPropVariant, SnPropParams> kPropKernels[] = {SN_PROP_VARIANTS(SN_X)};
+#undef SN_X
+#define SN_X(...) {{__VA_ARGS__}, &sn_normals_kernel<__VA_ARGS__>},
+const KernelEntry<SnNormalsVariant, SnNormalsParams> kNormalsKernels[] = {SN_NORMALS_VARIANTS(SN_X)};
+#undef SN_X
+
+// selection -> kernel.  A refusal is returned as it is; a selection that is not built is a bug in sn_variant.h: an error, never another kernel.
+template <typename V, typename P, size_t N>
+int pick_kernel(SnHandle h, const SnSelection<V>& sel, const KernelEntry<V, P> (&table)[N], const char* kernel, void (*&fn)(P)) {
+    if (sel.err) return fail(h, sel.err, sel.text);
+    for (const KernelEntry<V, P>& e : table)
+        if (sn_same_variant(e.v, sel.v)) {
+            fn = e.fn;
+            return SN_OK;
+        }
+    return fail(h, SN_ERR_INVALID, std::string("internal: the selected instantiation of ") + kernel + " is not in the list sn_variant.h builds");
+}
+// the one launch statement of the three kernels (the caller checks hipGetLastError)
+template <typename P>
+void launch_kernel(void (*fn)(P), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, P& p) {
+    void* args[] = {&p};
+    (void)hipLaunchKernel((const void*)fn, grid, block, args, lds_bytes, st);
 }
 
 }  // namespace
@@ -1095,10 +1110,11 @@ size_t sn_workspace_bytes(SnHandle h, int32_t height, int32_t width, const SnRen
 }
 
 // K2: proposal sampler (rows a8-a12) -> final euclidean bins [tile][S+1][64] in the workspace.  Shared by the colour render and
-// the normals render.
+// the normals render, which select (sn_select_proposal) and look the kernel up before they enqueue anything.
 static int launch_proposals(SnHandle h, const float* origins, const float* directions, const float* nears, const float* fars,
                             int32_t height, int32_t width, const SnRenderOpts* opts, const WorkspacePlan& wp, const TileGeom& g, char* ws,
-                            float* prop_depth_0, float* prop_depth_1, hipStream_t st, float** ebins_out, const SnDebugDump* dump = nullptr) {
+                            float* prop_depth_0, float* prop_depth_1, hipStream_t st, float** ebins_out, const SnPropSelection& sel,
+                            void (*kernel)(SnPropParams), const SnDebugDump* dump = nullptr) {
     const SnFieldDesc& d = h->desc;
     const int nprop = opts->num_proposal_iterations;
     const float* d_sbins = opts->initial_spacing_bins;
@@ -1144,7 +1160,7 @@ static int launch_proposals(SnHandle h, const float* origins, const float* direc
         pp.wpack[i] = (const float*)h->wpack_prop[i].ptr;
         pp.tables[i] = (const float*)h->table_prop[i].ptr;
         pp.table_bytes[i] = (uint32_t)h->table_prop[i].bytes;
-        pp.grid[i] = grid_levels(d.proposals[i]);
+        pp.grid[i] = sel.copies ? h->dense_res_prop[i] : grid_levels(d.proposals[i]);
         pp.feat_scale[i] = h->feat_scale_prop[i];
         pp.dense[i] = h->dense_info_prop[i];
         pp.log2_t[i] = d.proposals[i].log2_hashmap_size;
@@ -1157,46 +1173,13 @@ static int launch_proposals(SnHandle h, const float* origins, const float* direc
     pp.avg_density = d.average_init_density;
     pp.hist_pad = d.histogram_padding;
     const dim3 pgrid((unsigned)wp.prop_blocks), pblock(64 * SN_PROP_WAVES);
-    // the non-default sampler / position map (SnRenderOpts.spacing_mode, SnFieldDesc.disable_scene_contraction) run in their own
-    // instantiations -- the run-time-generic ones: uploaded tables, no de-hashed copies -- so the production kernels' code does not change
-    const bool alt = needs_generic_kernels(h, opts);
-    if (dump && alt) return fail(h, SN_ERR_INVALID, "sn_render_rays_debug: the dump exists for the default sampler and scene contraction only");
-    if (pp.march_stats && (dump || alt || d.proposals[0].grid_mode != 0 || !(nprop == 2 && h->nd_prop[0] == 5 && h->nd_prop[1] == 4)))
-        return fail(h, SN_ERR_INVALID, "SnRenderOpts.march_stats: the counting instantiation of the proposal kernel exists for the default variant only (torch grid, 2 nets, 5 + 4 de-hashed levels, default sampler)");
-    if (alt) {
-        if (d.proposals[0].grid_mode == 1) hipLaunchKernelGGL((sn_proposal_kernel<1, -1, -1, false, true>), pgrid, pblock, 0, st, pp);
-        else hipLaunchKernelGGL((sn_proposal_kernel<0, -1, -1, false, true>), pgrid, pblock, 0, st, pp);
-    } else
-    if (dump) {
-        // the instrumented instantiation exists for the production variant of nerfacto's proposal nets only
-        if (!(d.proposals[0].grid_mode == 0 && nprop == 2 && h->nd_prop[0] == 5 && h->nd_prop[1] == 4))
-            return fail(h, SN_ERR_INVALID, "sn_render_rays_debug: the proposal-kernel dump exists for the default variant only (torch grid, 2 nets, 5 + 4 de-hashed levels)");
+    if (sel.v.dump)
         for (int i = 0; i < SN_MAX_PROPOSALS; ++i) {
             pp.dump_fetch[i] = dump->prop_fetch[i];
             pp.dump_pdf[i] = dump->pdf_index[i];
             pp.dump_q[i] = dump->prop_q[i];
         }
-        for (int i = 0; i < nprop; ++i) pp.grid[i] = h->dense_res_prop[i];
-        hipLaunchKernelGGL((sn_proposal_kernel<0, 5, 4, true>), pgrid, pblock, 0, st, pp);
-    } else
-    if (d.proposals[0].grid_mode == 1) {
-        // nerfacto's proposal nets (max_res 128 / 256): 5 and 4 levels have de-hashed copies, which must cover every level tiny-cuda-nn
-        // indexes densely (3 and 2 at T = 2^17); other shapes read the uploaded tables with the per-level run-time decision
-        const int td0 = leading_dense(d.proposals[0]), td1 = nprop > 1 ? leading_dense(d.proposals[1]) : 0;
-        if (nprop == 2 && h->nd_prop[0] == 5 && h->nd_prop[1] == 4 && td0 >= 0 && td0 <= 5 && td1 >= 0 && td1 <= 4) {
-            for (int i = 0; i < nprop; ++i) pp.grid[i] = h->dense_res_prop[i];
-            hipLaunchKernelGGL((sn_proposal_kernel<1, 5, 4>), pgrid, pblock, 0, st, pp);
-        } else {
-            hipLaunchKernelGGL((sn_proposal_kernel<1, -1, -1>), pgrid, pblock, 0, st, pp);
-        }
-    } else if (nprop == 2 && h->nd_prop[0] == 5 && h->nd_prop[1] == 4) {
-        // nerfacto's nets (max_res 128 / 256): every level but the finest of the second net has a de-hashed copy
-        for (int i = 0; i < nprop; ++i) pp.grid[i] = h->dense_res_prop[i];
-        if (pp.march_stats) hipLaunchKernelGGL((sn_proposal_kernel<0, 5, 4, false, false, true>), pgrid, pblock, 0, st, pp);   // (the counting instantiation)
-        else hipLaunchKernelGGL((sn_proposal_kernel<0, 5, 4>), pgrid, pblock, 0, st, pp);
-    } else {
-        hipLaunchKernelGGL((sn_proposal_kernel<0, -1, -1>), pgrid, pblock, 0, st, pp);
-    }
+    launch_kernel(kernel, pgrid, pblock, 0, st, pp);
     SN_HIP(h, hipGetLastError());
     *ebins_out = d_ebins;
     return SN_OK;
@@ -1217,6 +1200,17 @@ static int render_rays_impl(SnHandle h, const float* origins, const float* direc
     WorkspacePlan wp = plan_workspace(height, width, *opts, h->n_cus, true);
     if (!opts->workspace || opts->workspace_bytes < wp.total)
         return fail(h, SN_ERR_WORKSPACE, "sn_render_rays: workspace too small, need " + std::to_string(wp.total) + " bytes");
+    // the instantiations are selected, and every refusal that depends on the options is made, BEFORE anything is enqueued (a
+    // call must not return SN_ERR_INVALID with the proposal kernel already enqueued and its counters half updated)
+    const SnVariantFacts vf = variant_facts(h);
+    const SnVariantRequest vr = variant_request(*opts, dump != nullptr);
+    const SnMainSelection sel = sn_select_main(vf, vr);  // (with proposal iterations: the proposal kernel's refusals too)
+    const SnPropSelection psel = sn_select_proposal(vf, vr);
+    void (*k1)(SnMainParams) = nullptr;
+    void (*k2)(SnPropParams) = nullptr;
+    if (int rc = pick_kernel(h, sel, kMainKernels, "sn_render_main_kernel", k1)) return rc;
+    if (vr.num_proposal_iterations > 0)
+        if (int rc = pick_kernel(h, psel, kPropKernels, "sn_proposal_kernel", k2)) return rc;
     hipStream_t st = (hipStream_t)stream;
     RenderGuard guard(h, st);  // waits for the handle's last weight upload; records this render for later uploads (opt-in: process-wide chain)
     char* ws = (char*)opts->workspace;
@@ -1235,20 +1229,11 @@ static int render_rays_impl(SnHandle h, const float* origins, const float* direc
         SN_HIP(h, hipMemsetAsync(d_minmax + wp.n_chunks, 0x00, (size_t)wp.n_chunks * 4, st));
     }
 
-    // every refusal that depends on the options comes BEFORE the first launch (a call must not return SN_ERR_INVALID with the
-    // proposal kernel already enqueued and its counters half updated)
-    if (opts->march_stats) {
-        const bool tcnn_ = d.main_field.grid_mode == 1, alt_ = needs_generic_kernels(h, opts);
-        const bool split_ = opts->precision >= 1 && h->split_ok, half1_ = split_ && opts->precision == 2;
-        if (half1_ || dump || alt_)
-            return fail(h, SN_ERR_INVALID, "SnRenderOpts.march_stats: no counting instantiation for this variant (single fp16 / instrumented / generic sampler)");
-        if (!(split_ && !tcnn_ && h->nd_torch == SN_DENSE_LEVELS_DEFAULT))
-            return fail(h, SN_ERR_INVALID, "SnRenderOpts.march_stats: the counting instantiation of the main kernel exists for the default variant only (torch grid, 11 de-hashed levels, precision 1)");
-    }
     clear_stamp(ws);  // whatever this workspace held is being overwritten
     float* d_ebins = nullptr;
     if (nprop > 0)
-        if (int rc = launch_proposals(h, origins, directions, nears, fars, height, width, opts, wp, g, ws, prop_depth_0, prop_depth_1, st, &d_ebins, dump))
+        if (int rc = launch_proposals(h, origins, directions, nears, fars, height, width, opts, wp, g, ws, prop_depth_0, prop_depth_1, st, &d_ebins, psel, k2,
+                                      dump))
             return rc;
 
     SnMainParams p;
@@ -1262,9 +1247,7 @@ static int render_rays_impl(SnHandle h, const float* origins, const float* direc
     p.spacing_uniform = opts->spacing_mode;
     p.pm = h->pos_map;
     p.table = (const float*)h->table_main.ptr;
-    const bool split = opts->precision >= 1 && h->split_ok;  // (a handle whose weights cannot be range-conditioned renders in exact fp32)
-    const bool half1 = split && opts->precision == 2;       // single fp16 (sn_main.h sn_main_field_f16): tiny-cuda-nn grids only (valid_opts)
-    p.wimg = (const float*)(split ? h->wimg_main_h.ptr : h->wimg_main.ptr);
+    p.wimg = (const float*)(sel.split ? h->wimg_main_h.ptr : h->wimg_main.ptr);
     p.feat_scale = h->feat_scale_main;
     p.hquads = h->hquads_info;
     p.hrows = (const float*)h->hrows_main.ptr;
@@ -1297,23 +1280,19 @@ static int render_rays_impl(SnHandle h, const float* origins, const float* direc
     p.early_term = h->sw.early_term.load(std::memory_order_relaxed);
     p.march_stats = (unsigned long long*)opts->march_stats;
     for (int c = 0; c < 3; ++c) p.bg[c] = opts->background_rgb[c];
-    const bool tcnn = d.main_field.grid_mode == 1;
-    // de-hashed copies are used when they cover every level tiny-cuda-nn indexes densely (always true for torch grids and for nerfacto's
-    // tcnn shapes); otherwise the run-time variant (ND = -1) reads the uploaded table
-    const int td = tcnn ? leading_dense(d.main_field) : 0;
-    const bool alt = needs_generic_kernels(h, opts);  // (launch_proposals: the generic instantiations)
-    const bool use_copies = !alt && h->nd_torch > 0 && (!tcnn || (td >= 0 && td <= h->nd_torch));
-    p.grid = grid_levels(d.main_field);
-    if (use_copies) {
-        p.grid = h->dense_res;
-        p.dense = h->dense_info;
+    p.grid = sel.copies && (!sel.half1 || sel.hgrid) ? h->dense_res : grid_levels(d.main_field);
+    if (sel.copies) p.dense = h->dense_info;
+    if (sel.v.dump) {
+        p.dump_fetch = dump->main_fetch;
+        p.dump_q = dump->main_q;
+        p.dump_median = dump->median_index;
     }
     const int gbx = (g.tiles_x + 1) / 2, gby = (g.tiles_y + 1) / 2;
     // weight image + (uniform sampler) the frame's S + 1 euclidean bins
     const size_t etab_bytes = nprop == 0 ? ((size_t)opts->num_nerf_samples + 1 + 3) / 4 * 16 : 0;
-    const size_t lds_bytes = (half1 ? (size_t)SnMainImgF16::TOTAL_BYTES : (size_t)SnMainImg::TOTAL * 4) + etab_bytes;
+    const size_t lds_bytes = (sel.half1 ? (size_t)SnMainImgF16::TOTAL_BYTES : (size_t)SnMainImg::TOTAL * 4) + etab_bytes;
     // split-depth tail (plan_tail): the workgroups of the last, partly filled round become n_seg segment jobs each
-    const bool tail_split = !dump && !half1 && !h->sw.tail_split_off.load(std::memory_order_relaxed) && wp.n_seg > 1;
+    const bool tail_split = !dump && !sel.half1 && !h->sw.tail_split_off.load(std::memory_order_relaxed) && wp.n_seg > 1;
     p.seg_first_block = gbx * gby;
     p.n_seg = 1;
     p.seg_len = opts->num_nerf_samples;
@@ -1326,75 +1305,7 @@ static int render_rays_impl(SnHandle h, const float* origins, const float* direc
         p.seg_scratch = (f32x4*)(ws + wp.off_seg);
     }
     const dim3 grid((unsigned)(gbx * gby - n_tail + ((n_tail + 7) / 8 * 8) * p.n_seg)), block(256);  // (segment jobs: the tail padded to whole XCD rows)
-#define SN_LAUNCH_MAIN(MODE, PREC, GRID, ND) \
-    hipLaunchKernelGGL((sn_render_main_kernel<MODE, PREC, GRID, ND>), grid, block, lds_bytes, st, p)
-    const int nd_launch = use_copies ? h->nd_torch : -1;
-#define SN_LAUNCH_MAIN_ND(MODE, PREC, GRID)                          \
-    switch (nd_launch) { /* the copy counts sn_finalize_weights can leave a handle with */ \
-        case SN_BC_MAIN: SN_LAUNCH_MAIN(MODE, PREC, GRID, SN_BC_MAIN); break;       \
-        case SN_DENSE_LEVELS_DEFAULT: SN_LAUNCH_MAIN(MODE, PREC, GRID, SN_DENSE_LEVELS_DEFAULT); break;     \
-        default: SN_LAUNCH_MAIN(MODE, PREC, GRID, -1); break;     \
-    }
-#define SN_LAUNCH_MAIN_TORCH(MODE, PREC) SN_LAUNCH_MAIN_ND(MODE, PREC, 0)
-#define SN_LAUNCH_MAIN_TCNN(MODE, PREC) SN_LAUNCH_MAIN_ND(MODE, PREC, 1)
-    if (p.march_stats && (half1 || dump || alt))
-        return fail(h, SN_ERR_INVALID, "SnRenderOpts.march_stats: no counting instantiation for this variant (single fp16 / instrumented / generic sampler)");
-    if (half1) {
-        // single-fp16 mode: the tiny-cuda-nn grid's kernels, with the de-hashed copies when the handle has the default 11 of them
-        if (dump || alt) return fail(h, SN_ERR_INVALID, "precision 2 (single fp16) has no instrumented / generic-sampler instantiation");
-        // ND = 11: the grid from its fp16 storage (SnFieldDesc.half_grid); otherwise the run-time variant on the uploaded fp32 table with every
-        // row rounded through fp16 on the fly -- the same values
-        const bool hgrid = nd_launch == 11 && h->hquads_main.ptr && h->hrows_main.ptr;
-        if (!hgrid) p.grid = grid_levels(d.main_field);
-        if (nprop > 0) {
-            if (hgrid) SN_LAUNCH_MAIN(1, 2, 1, 11); else SN_LAUNCH_MAIN(1, 2, 1, -1);
-        } else {
-            if (hgrid) SN_LAUNCH_MAIN(0, 2, 1, 11); else SN_LAUNCH_MAIN(0, 2, 1, -1);
-        }
-    } else
-    if (dump) {
-        // instrumented instantiations: the production variant (torch grid, 11 de-hashed levels), both samplers, both precisions
-        if (tcnn || h->nd_torch != 11 || alt)
-            return fail(h, SN_ERR_INVALID, "sn_render_rays_debug: the main-kernel dump exists for the default variant only (torch grid, 11 de-hashed levels, default sampler and scene contraction)");
-        p.dump_fetch = dump->main_fetch;
-        p.dump_q = dump->main_q;
-        p.dump_median = dump->median_index;
-        if (nprop > 0) {
-            if (split) hipLaunchKernelGGL((sn_render_main_kernel<1, 1, 0, 11, true>), grid, block, lds_bytes, st, p);
-            else hipLaunchKernelGGL((sn_render_main_kernel<1, 0, 0, 11, true>), grid, block, lds_bytes, st, p);
-        } else {
-            if (split) hipLaunchKernelGGL((sn_render_main_kernel<0, 1, 0, 11, true>), grid, block, lds_bytes, st, p);
-            else hipLaunchKernelGGL((sn_render_main_kernel<0, 0, 0, 11, true>), grid, block, lds_bytes, st, p);
-        }
-    } else if (alt) {
-#define SN_LAUNCH_MAIN_ALT(MODE, PREC, GRID) hipLaunchKernelGGL((sn_render_main_kernel<MODE, PREC, GRID, -1, false, true>), grid, block, lds_bytes, st, p)
-        if (nprop > 0) {
-            if (split) { if (tcnn) SN_LAUNCH_MAIN_ALT(1, 1, 1); else SN_LAUNCH_MAIN_ALT(1, 1, 0); }
-            else { if (tcnn) SN_LAUNCH_MAIN_ALT(1, 0, 1); else SN_LAUNCH_MAIN_ALT(1, 0, 0); }
-        } else {
-            if (split) { if (tcnn) SN_LAUNCH_MAIN_ALT(0, 1, 1); else SN_LAUNCH_MAIN_ALT(0, 1, 0); }
-            else { if (tcnn) SN_LAUNCH_MAIN_ALT(0, 0, 1); else SN_LAUNCH_MAIN_ALT(0, 0, 0); }
-        }
-#undef SN_LAUNCH_MAIN_ALT
-    } else
-    if (p.march_stats) {
-        // the counting instantiations (diagnostics): the production variant of nerfacto's torch grid, split precision, both samplers
-        if (!(split && !tcnn && nd_launch == SN_DENSE_LEVELS_DEFAULT))
-            return fail(h, SN_ERR_INVALID, "SnRenderOpts.march_stats: the counting instantiation of the main kernel exists for the default variant only (torch grid, 11 de-hashed levels, precision 1)");
-        if (nprop > 0) hipLaunchKernelGGL((sn_render_main_kernel<1, 1, 0, SN_DENSE_LEVELS_DEFAULT, false, false, true>), grid, block, lds_bytes, st, p);
-        else hipLaunchKernelGGL((sn_render_main_kernel<0, 1, 0, SN_DENSE_LEVELS_DEFAULT, false, false, true>), grid, block, lds_bytes, st, p);
-    } else
-    if (nprop > 0) {
-        if (split) { if (tcnn) { SN_LAUNCH_MAIN_TCNN(1, 1) } else { SN_LAUNCH_MAIN_TORCH(1, 1) } }
-        else { if (tcnn) { SN_LAUNCH_MAIN_TCNN(1, 0) } else { SN_LAUNCH_MAIN_TORCH(1, 0) } }
-    } else {
-        if (split) { if (tcnn) { SN_LAUNCH_MAIN_TCNN(0, 1) } else { SN_LAUNCH_MAIN_TORCH(0, 1) } }
-        else { if (tcnn) { SN_LAUNCH_MAIN_TCNN(0, 0) } else { SN_LAUNCH_MAIN_TORCH(0, 0) } }
-    }
-#undef SN_LAUNCH_MAIN_TCNN
-#undef SN_LAUNCH_MAIN_TORCH
-#undef SN_LAUNCH_MAIN_ND
-#undef SN_LAUNCH_MAIN
+    launch_kernel(k1, grid, block, lds_bytes, st, p);
     SN_HIP(h, hipGetLastError());
     if (tail_split) {
         if (nprop > 0) hipLaunchKernelGGL((sn_main_combine_kernel<1>), dim3((unsigned)n_tail), block, 0, st, p);
@@ -1426,14 +1337,8 @@ int sn_render_rays_debug(SnHandle h, const float* origins, const float* directio
 }
 
 int sn_effective_precision(SnHandle h, int32_t requested, int32_t kernel) {
-    if (!h || requested < 0 || requested > 2 || (kernel != 0 && kernel != 1)) return -1;
-    if (!h->finalized) return -1;
-    if (requested == 0) return 0;
-    if (requested == 2) {  // single fp16: the render / field kernels of a tiny-cuda-nn grid; the normals kernel keeps the split form
-        if (h->desc.main_field.grid_mode != 1) return -1;
-        if (kernel == 0) return h->split_ok ? 2 : 0;
-    }
-    return (kernel == 0 ? h->split_ok : h->normals_split_ok) ? 1 : 0;
+    if (!h || !h->finalized) return -1;
+    return sn_effective_precision_of(variant_facts(h), requested, kernel);
 }
 
 int sn_debug_layout(SnHandle h, int32_t which, SnDebugLayout* out) {
@@ -1540,6 +1445,17 @@ int sn_render_normals(SnHandle h, const float* origins, const float* directions,
     const WorkspacePlan wp = plan_workspace(height, width, *opts, h->n_cus, true);
     if (!opts->workspace || opts->workspace_bytes < wp.total)
         return fail(h, SN_ERR_WORKSPACE, "sn_render_normals: workspace too small, need " + std::to_string(wp.total) + " bytes");
+    // selected before anything is enqueued; the proposal kernel (and its refusals) only when this call samples its own bins
+    const SnVariantFacts vf = variant_facts(h);
+    const SnVariantRequest vr = variant_request(*opts, false);
+    const SnNormalsSelection sel = sn_select_normals(vf, vr);
+    const bool own_bins = vr.num_proposal_iterations > 0 && !opts->reuse_final_bins;
+    const SnPropSelection psel = sn_select_proposal(vf, vr);
+    void (*k3)(SnNormalsParams) = nullptr;
+    void (*k2)(SnPropParams) = nullptr;
+    if (own_bins)
+        if (int rc = pick_kernel(h, psel, kPropKernels, "sn_proposal_kernel", k2)) return rc;
+    if (int rc = pick_kernel(h, sel, kNormalsKernels, "sn_normals_kernel", k3)) return rc;
     hipStream_t st = (hipStream_t)stream;
     RenderGuard guard(h, st);
     char* ws = (char*)opts->workspace;
@@ -1557,7 +1473,8 @@ int sn_render_normals(SnHandle h, const float* origins, const float* directions,
             d_ebins = (float*)(ws + wp.off_ebins);
         } else {
             clear_stamp(ws);
-            if (int rc = launch_proposals(h, origins, directions, nears, fars, height, width, opts, wp, g, ws, nullptr, nullptr, st, &d_ebins)) return rc;
+            if (int rc = launch_proposals(h, origins, directions, nears, fars, height, width, opts, wp, g, ws, nullptr, nullptr, st, &d_ebins, psel, k2))
+                return rc;
             stamp_workspace(ws, want);  // (the proposal kernel is deterministic: these ARE the bins a colour render of the same call would leave)
         }
     } else {
@@ -1574,7 +1491,7 @@ int sn_render_normals(SnHandle h, const float* origins, const float* directions,
     p.spacing_uniform = opts->spacing_mode;
     p.pm = h->pos_map;
     p.table = (const float*)h->table_main.ptr;
-    const bool split = opts->precision >= 1 && h->normals_split_ok;  // (precision 2: the normals kernel keeps the split form)
+    const bool split = sel.split;
     p.wimg = (const float*)(split ? h->wimg_normals_h.ptr : h->wimg_normals.ptr);
     p.normals = normals;
     p.pred_normals = pred_normals;
@@ -1595,34 +1512,13 @@ int sn_render_normals(SnHandle h, const float* origins, const float* directions,
     const int gbx = (g.tiles_x + 1) / 2, gby = (g.tiles_y + 1) / 2;
     const size_t lds_bytes = split ? (size_t)SnNormImgH::TOTAL_BYTES : (size_t)SnNormImg::TOTAL * 4;
     const dim3 grid((unsigned)(gbx * gby)), block(256);
-    const bool tcnn = d.main_field.grid_mode == 1;
-#define SN_LAUNCH_NORMALS(MODE, GRID, ND)                                                                      \
-    if (split) hipLaunchKernelGGL((sn_normals_kernel<MODE, GRID, 1, ND>), grid, block, lds_bytes, st, p);      \
-    else hipLaunchKernelGGL((sn_normals_kernel<MODE, GRID, 0, ND>), grid, block, lds_bytes, st, p)
-    // nerfacto's torch grid with its default 11 de-hashed levels reads them (168 gathers per step instead of 256); other shapes and the
-    // tiny-cuda-nn grid read the uploaded table
-    const bool alt = needs_generic_kernels(h, opts);
-    const bool copies = !alt && !tcnn && h->nd_torch == 11 && h->dense_main.ptr;
-    if (copies) {
+    if (sel.copies) {
         p.dense = h->dense_info;
         p.inv_feat_scale = 1.0f / h->feat_scale_main;
     }
     p.feat_scale = split ? h->feat_scale_main : 1.0f;
     p.grad_scale = split ? h->grad_scale_normals : 1.0f;
-#define SN_LAUNCH_NORMALS_ALT(MODE, GRID)                                                                         \
-    if (split) hipLaunchKernelGGL((sn_normals_kernel<MODE, GRID, 1, -1, true>), grid, block, lds_bytes, st, p);   \
-    else hipLaunchKernelGGL((sn_normals_kernel<MODE, GRID, 0, -1, true>), grid, block, lds_bytes, st, p)
-    if (alt) {
-        if (nprop > 0) { if (tcnn) { SN_LAUNCH_NORMALS_ALT(1, 1); } else { SN_LAUNCH_NORMALS_ALT(1, 0); } }
-        else { if (tcnn) { SN_LAUNCH_NORMALS_ALT(0, 1); } else { SN_LAUNCH_NORMALS_ALT(0, 0); } }
-    } else
-    if (nprop > 0) {
-        if (tcnn) { SN_LAUNCH_NORMALS(1, 1, -1); } else if (copies) { SN_LAUNCH_NORMALS(1, 0, 11); } else { SN_LAUNCH_NORMALS(1, 0, -1); }
-    } else {
-        if (tcnn) { SN_LAUNCH_NORMALS(0, 1, -1); } else if (copies) { SN_LAUNCH_NORMALS(0, 0, 11); } else { SN_LAUNCH_NORMALS(0, 0, -1); }
-    }
-#undef SN_LAUNCH_NORMALS_ALT
-#undef SN_LAUNCH_NORMALS
+    launch_kernel(k3, grid, block, lds_bytes, st, p);
     SN_HIP(h, hipGetLastError());
     return SN_OK;
 }
