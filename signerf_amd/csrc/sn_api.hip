@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "sn_device.h"
+#include "sn_frame.h"
 #include "sn_main.h"
 #include "sn_mask.h"
 #include "sn_mesh.h"
@@ -582,112 +583,6 @@ int build_pairs(SnHandle h, const SnHashMlpDesc& d, const DevBuf& table, DevBuf&
     return SN_OK;
 }
 
-struct TileGeom {
-    int tw_log2, th_log2, tiles_x, tiles_y;
-};
-
-TileGeom tile_geometry(int height, int width) {
-    TileGeom g;
-    if (height >= 8) {
-        g.tw_log2 = 3;
-        g.th_log2 = 3;
-    } else {
-        g.tw_log2 = 6;
-        g.th_log2 = 0;
-    }
-    g.tiles_x = (width + (1 << g.tw_log2) - 1) >> g.tw_log2;
-    g.tiles_y = (height + (1 << g.th_log2) - 1) >> g.th_log2;
-    return g;
-}
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct WorkspacePlan {
-    size_t off_exp_raw, off_minmax, off_ebins, off_prop_scratch, off_prop_counter, off_seg, total;
-    int prop_blocks;
-    int n_chunks;
-    int seg_first_block, n_seg, seg_len;  // split-depth tail of the main kernel (n_seg <= 1: none)
-};
-
-// Split-depth tail of the main kernel (sn_main.h SnMainParams).  A launch is whole workgroups (2x2 tiles, 4 waves) on a fixed number of
-// slots (CUs x SN_MAIN_WAVES_PER_SIMD workgroups = 768): its last round may hold a handful of workgroups -- a 64x64 viewer frame is 16 of
-// them, the tail of a 640x640 frame 64 -- each still marching all S samples with the chip nearly empty.  Such a tail's workgroups are cut
-// into n segment jobs of ceil(S / n) samples, so that the round fills more of the chip and is ~1/n as long; a small kernel composites
-// the stored samples in order (bit-identical).
-// WHEN (measured r03, frames back to back on one stream, profiles/r03_tail_split.txt): it pays when the tail is SMALL -- at most 1/8 of
-// the slots: 64x64 0.79 -> 0.25 ms, 128x128 0.69 -> 0.41, 640x640 2.06 -> 1.88 (-9 %).  A tail that already fills a quarter of the chip
-// gains nothing or loses: its lone waves step ~2x faster than waves that share a SIMD AND run at the boost clock (the chip is power-
-// limited when full), segment jobs pay the prologue n times -- 800x800 (196 of 768) -1 % per launch but +1 % with two frames in flight,
-// 200x200 (169) +11 %, 512x512 (256) +8 %.  So: tails above slots / 8 stay whole.
-// n minimises a cost model in units of sample steps: rounds of jobs x (samples per job + ~1.5 steps of prologue), a partly filled round
-// priced at 0.25 + 0.75 x fill.
-struct TailPlan {
-    int first_block, n_seg, seg_len;
-};
-TailPlan plan_tail(int total_wgs, int n_cus, int S, bool enabled) {
-    TailPlan t{total_wgs, 1, S};
-    const int slots = n_cus * SN_MAIN_WAVES_PER_SIMD;
-    if (!enabled || slots <= 0 || S < 8) return t;
-    const int tail = total_wgs % slots;
-    if (tail == 0 || tail > slots / 8) return t;
-    auto cost = [&](int n) {
-        const long jobs = (long)tail * n;
-        const double len = (double)((S + n - 1) / n) + 1.5;
-        const long full = jobs / slots, rest = jobs % slots;
-        return (double)full * len + (rest ? len * (0.25 + 0.75 * (double)rest / slots) : 0.0) + 0.5 * (n - 1);  // (+ a little per extra segment: scratch, launch)
-    };
-    int best = 1;
-    double best_cost = cost(1);
-    for (int n = 2; n <= 8 && (S + n - 1) / n >= 4; ++n)
-        if (cost(n) < best_cost - 1e-9) {
-            best = n;
-            best_cost = cost(n);
-        }
-    if (best == 1 || best_cost > 0.9 * cost(1)) return t;  // not worth a second kernel
-    t.first_block = total_wgs - tail;
-    if (t.first_block % 8 != 0) return TailPlan{total_wgs, 1, S};  // (the XCD-affine job order needs whole rows of 8 in front; true for 256 CUs)
-    t.n_seg = best;
-    t.seg_len = (S + best - 1) / best;
-    return t;
-}
-
-WorkspacePlan plan_workspace(int height, int width, const SnRenderOpts& o, int n_cus, bool tail_split) {
-    WorkspacePlan w;
-    const size_t n = (size_t)height * width;
-    const TileGeom g = tile_geometry(height, width);
-    size_t off = 0;
-    w.off_exp_raw = off;
-    off += align256(n * 4);
-    w.n_chunks = (int)((n + (size_t)o.chunk_rays - 1) / (size_t)o.chunk_rays);
-    w.off_minmax = off;
-    off += align256((size_t)w.n_chunks * 8);
-    w.off_ebins = off;
-    w.off_prop_scratch = off;
-    w.off_prop_counter = off;
-    w.prop_blocks = 0;
-    if (o.num_proposal_iterations > 0) {
-        off += align256((size_t)g.tiles_x * g.tiles_y * 64 * (o.num_nerf_samples + 1) * 4);
-        // persistent proposal waves: what the chip holds (256 CUs x SN_PROP_WG_PER_CU workgroups of SN_PROP_WAVES waves), at most one per tile
-        const int ntiles = g.tiles_x * g.tiles_y;
-        w.prop_blocks = std::min((ntiles + SN_PROP_WAVES - 1) / SN_PROP_WAVES, 256 * SN_PROP_WG_PER_CU);
-        w.off_prop_scratch = off;
-        off += align256((size_t)w.prop_blocks * SN_PROP_WAVES * SN_PROP_SCRATCH_FLOATS * 4);
-        w.off_prop_counter = off;   // the proposal kernel's tile queue (one uint32, zeroed per launch)
-        off += 256;
-    }
-    {
-        const int gbx = (g.tiles_x + 1) / 2, gby = (g.tiles_y + 1) / 2;
-        const TailPlan t = plan_tail(gbx * gby, n_cus, o.num_nerf_samples, tail_split);
-        w.seg_first_block = t.first_block;
-        w.n_seg = t.n_seg;
-        w.seg_len = t.seg_len;
-        w.off_seg = off;
-        if (t.n_seg > 1) off += align256((size_t)(gbx * gby - t.first_block) * 4 * (size_t)o.num_nerf_samples * 64 * 16);  // (density, r, g, b) per sample
-    }
-    w.total = off;
-    return w;
-}
-
 // ---- launch selection (sn_variant.h) --------------------------------------------------------------------------------------------------
 // what selection depends on: the finalized handle's side ...
 SnVariantFacts variant_facts(SnHandle h) {
@@ -746,6 +641,52 @@ template <typename P>
 void launch_kernel(void (*fn)(P), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, P& p) {
     void* args[] = {&p};
     (void)hipLaunchKernel((const void*)fn, grid, block, args, lds_bytes, st);
+}
+
+// What the two render entry points share, for the entry point `who`, in two pieces (sn_render_normals returns early between them):
+// begin_render checks the arguments, adopts SnRenderOpts into `own` and validates it against the finalized handle -- `pred_normals`
+// says that the call wants the predicted-normals head -- and plan_render plans the frame (sn_frame.h) and checks the workspace.
+int begin_render(const char* who, SnHandle h, const float* origins, const float* directions, const float* nears, const float* fars,
+                 int32_t height, int32_t width, const SnRenderOpts* opts, bool pred_normals, SnRenderOpts& own) {
+    if (!h) return SN_ERR_INVALID;
+    auto refuse = [&](int code, const std::string& text) { return fail(h, code, who + (": " + text)); };
+    if (!origins || !directions || !opts || height <= 0 || width <= 0) return refuse(SN_ERR_INVALID, "bad argument");
+    if (int rc = adopt_struct(h, opts, kRenderOptsMin, own, (who + std::string(": SnRenderOpts")).c_str())) return rc;
+    if ((nears == nullptr) != (fars == nullptr)) return refuse(SN_ERR_INVALID, "nears and fars must both be given or both be NULL");
+    if (!h->finalized) return refuse(SN_ERR_STATE, "weights not finalized");
+    if (pred_normals && !h->has_pred_normals) return refuse(SN_ERR_STATE, "field.mlp_pred_normals.* / field.field_head_pred_normals.net.* not uploaded");
+    std::string why;
+    if (!valid_opts(h->desc, own, why)) return refuse(SN_ERR_INVALID, why);
+    return SN_OK;
+}
+
+int plan_render(const char* who, SnHandle h, int32_t height, int32_t width, const SnRenderOpts& opts, SnFramePlan& plan) {
+    plan = sn_plan_frame(height, width, opts, h->n_cus);
+    if (!opts.workspace || opts.workspace_bytes < plan.ws.total)
+        return fail(h, SN_ERR_WORKSPACE, who + (": workspace too small, need " + std::to_string(plan.ws.total) + " bytes"));
+    return SN_OK;
+}
+
+// zeroes a kernel's parameter block and fills the fields SnMainParams, SnPropParams and SnNormalsParams share by name
+template <typename P>
+void fill_frame_params(P& p, SnHandle h, const float* origins, const float* directions, const float* nears, const float* fars,
+                       const SnRenderOpts& opts, const SnFramePlan& plan) {
+    memset(&p, 0, sizeof(p));
+    p.origins = origins;
+    p.directions = directions;
+    p.nears = nears;
+    p.fars = fars;
+    p.height = plan.height;
+    p.width = plan.width;
+    p.tile_w_log2 = plan.g.tw_log2;
+    p.tile_h_log2 = plan.g.th_log2;
+    p.tiles_x = plan.g.tiles_x;
+    p.tiles_y = plan.g.tiles_y;
+    p.near_plane = opts.near_plane;
+    p.far_plane = opts.far_plane;
+    p.avg_density = h->desc.average_init_density;
+    p.spacing_uniform = opts.spacing_mode;
+    p.pm = h->pos_map;
 }
 
 }  // namespace
@@ -1104,54 +1045,33 @@ size_t sn_workspace_bytes(SnHandle h, int32_t height, int32_t width, const SnRen
     if (!h || !opts_in || height <= 0 || width <= 0) return 0;
     SnRenderOpts own;
     if (adopt_struct(h, opts_in, kRenderOptsMin, own, "sn_workspace_bytes: SnRenderOpts")) return 0;  // (the text is in sn_last_error)
-    const SnRenderOpts* opts = &own;
-    if (opts->chunk_rays < 1) return 0;
-    return plan_workspace(height, width, *opts, h->n_cus, true).total;  // (the size with the tail split on covers both settings of SN_TAIL_SPLIT)
+    if (own.chunk_rays < 1) return 0;
+    return sn_plan_frame(height, width, own, h->n_cus).ws.total;
 }
 
 // K2: proposal sampler (rows a8-a12) -> final euclidean bins [tile][S+1][64] in the workspace.  Shared by the colour render and
 // the normals render, which select (sn_select_proposal) and look the kernel up before they enqueue anything.
 static int launch_proposals(SnHandle h, const float* origins, const float* directions, const float* nears, const float* fars,
-                            int32_t height, int32_t width, const SnRenderOpts* opts, const WorkspacePlan& wp, const TileGeom& g, char* ws,
-                            float* prop_depth_0, float* prop_depth_1, hipStream_t st, float** ebins_out, const SnPropSelection& sel,
-                            void (*kernel)(SnPropParams), const SnDebugDump* dump = nullptr) {
+                            const SnRenderOpts* opts, const SnFramePlan& plan, char* ws, float* prop_depth_0, float* prop_depth_1, hipStream_t st,
+                            const SnPropSelection& sel, void (*kernel)(SnPropParams), const SnDebugDump* dump = nullptr) {
     const SnFieldDesc& d = h->desc;
     const int nprop = opts->num_proposal_iterations;
-    const float* d_sbins = opts->initial_spacing_bins;
-    float* d_ebins = (float*)(ws + wp.off_ebins);
     SnPropParams pp;
-    memset(&pp, 0, sizeof(pp));
-    pp.origins = origins;
-    pp.directions = directions;
-    pp.nears = nears;
-    pp.fars = fars;
-    pp.sbins0 = d_sbins;
+    fill_frame_params(pp, h, origins, directions, nears, fars, *opts, plan);
+    pp.sbins0 = opts->initial_spacing_bins;
     for (int i = 0; i < SN_MAX_PROPOSALS; ++i) pp.pdf_u[i] = opts->pdf_u[i];
-    pp.ebins_out = d_ebins;
-    pp.scratch = (float*)(ws + wp.off_prop_scratch);
-    {
-        // the tile queue of the persistent waves (sn_proposal.h): only when some wave gets more than one tile
-        const int n_waves = wp.prop_blocks * SN_PROP_WAVES, n_tiles = g.tiles_x * g.tiles_y;
-        pp.tile_counter = nullptr;
-        if (n_tiles > n_waves) {
-            pp.tile_counter = (unsigned int*)(ws + wp.off_prop_counter);
-            SN_HIP(h, hipMemsetD32Async((hipDeviceptr_t)pp.tile_counter, n_waves, 1, st));
-        }
+    pp.ebins_out = (float*)(ws + plan.ws.off_ebins);
+    pp.scratch = (float*)(ws + plan.ws.off_prop_scratch);
+    if (plan.prop_queue) {  // the tile queue of the persistent waves (sn_proposal.h)
+        pp.tile_counter = (unsigned int*)(ws + plan.ws.off_prop_counter);
+        SN_HIP(h, hipMemsetD32Async((hipDeviceptr_t)pp.tile_counter, plan.prop_queue_start, 1, st));
     }
     pp.cache_off = h->sw.prop_cache_off.load(std::memory_order_relaxed);
     pp.early_term = h->sw.early_term.load(std::memory_order_relaxed);
     pp.march_stats = (unsigned long long*)opts->march_stats;
-    pp.spacing_uniform = opts->spacing_mode;
-    pp.pm = h->pos_map;
     pp.pdf_ieee = h->sw.pdf_ieee.load(std::memory_order_relaxed);
     pp.prop_depth[0] = prop_depth_0;
     pp.prop_depth[1] = prop_depth_1;
-    pp.height = height;
-    pp.width = width;
-    pp.tile_w_log2 = g.tw_log2;
-    pp.tile_h_log2 = g.th_log2;
-    pp.tiles_x = g.tiles_x;
-    pp.tiles_y = g.tiles_y;
     pp.n_levels = nprop;
     for (int i = 0; i < nprop; ++i) {
         pp.pairs[i] = (const float*)h->pairs_prop[i].ptr;
@@ -1168,38 +1088,28 @@ static int launch_proposals(SnHandle h, const float* origins, const float* direc
         pp.n_samples[i] = opts->num_proposal_samples[i];
     }
     pp.n_final = opts->num_nerf_samples;
-    pp.near_plane = opts->near_plane;
-    pp.far_plane = opts->far_plane;
-    pp.avg_density = d.average_init_density;
     pp.hist_pad = d.histogram_padding;
-    const dim3 pgrid((unsigned)wp.prop_blocks), pblock(64 * SN_PROP_WAVES);
     if (sel.v.dump)
         for (int i = 0; i < SN_MAX_PROPOSALS; ++i) {
             pp.dump_fetch[i] = dump->prop_fetch[i];
             pp.dump_pdf[i] = dump->pdf_index[i];
             pp.dump_q[i] = dump->prop_q[i];
         }
-    launch_kernel(kernel, pgrid, pblock, 0, st, pp);
+    launch_kernel(kernel, dim3((unsigned)plan.prop_blocks), dim3((unsigned)plan.prop_threads), 0, st, pp);
     SN_HIP(h, hipGetLastError());
-    *ebins_out = d_ebins;
     return SN_OK;
 }
 
 static int render_rays_impl(SnHandle h, const float* origins, const float* directions, const float* nears, const float* fars, int32_t height,
                             int32_t width, const SnRenderOpts* opts, float* rgb, float* depth, float* accumulation, float* expected_depth,
                             float* prop_depth_0, float* prop_depth_1, const SnDebugDump* dump, SnStream stream) {
-    if (!h) return SN_ERR_INVALID;
-    if (!origins || !directions || !opts || height <= 0 || width <= 0) return fail(h, SN_ERR_INVALID, "sn_render_rays: bad argument");
+    const char* who = "sn_render_rays";
     SnRenderOpts opts_own;
-    if (int rc = adopt_struct(h, opts, kRenderOptsMin, opts_own, "sn_render_rays: SnRenderOpts")) return rc;
+    SnFramePlan plan;
+    if (int rc = begin_render(who, h, origins, directions, nears, fars, height, width, opts, false, opts_own)) return rc;
     opts = &opts_own;
-    if ((nears == nullptr) != (fars == nullptr)) return fail(h, SN_ERR_INVALID, "sn_render_rays: nears and fars must both be given or both be NULL");
-    if (!h->finalized) return fail(h, SN_ERR_STATE, "sn_render_rays: weights not finalized");
-    std::string why;
-    if (!valid_opts(h->desc, *opts, why)) return fail(h, SN_ERR_INVALID, "sn_render_rays: " + why);
-    WorkspacePlan wp = plan_workspace(height, width, *opts, h->n_cus, true);
-    if (!opts->workspace || opts->workspace_bytes < wp.total)
-        return fail(h, SN_ERR_WORKSPACE, "sn_render_rays: workspace too small, need " + std::to_string(wp.total) + " bytes");
+    if (int rc = plan_render(who, h, height, width, *opts, plan)) return rc;
+    const WorkspacePlan& wp = plan.ws;
     // the instantiations are selected, and every refusal that depends on the options is made, BEFORE anything is enqueued (a
     // call must not return SN_ERR_INVALID with the proposal kernel already enqueued and its counters half updated)
     const SnVariantFacts vf = variant_facts(h);
@@ -1215,11 +1125,9 @@ static int render_rays_impl(SnHandle h, const float* origins, const float* direc
     RenderGuard guard(h, st);  // waits for the handle's last weight upload; records this render for later uploads (opt-in: process-wide chain)
     char* ws = (char*)opts->workspace;
     const SnFieldDesc& d = h->desc;
-    const TileGeom g = tile_geometry(height, width);
     const int64_t n = (int64_t)height * width;
     const int nprop = opts->num_proposal_iterations;
 
-    const float* d_sbins = opts->initial_spacing_bins;  // null => kernels fall back to i/N
     uint32_t* d_minmax = nullptr;
     float* d_exp_raw = nullptr;
     if (expected_depth) {
@@ -1230,22 +1138,13 @@ static int render_rays_impl(SnHandle h, const float* origins, const float* direc
     }
 
     clear_stamp(ws);  // whatever this workspace held is being overwritten
-    float* d_ebins = nullptr;
     if (nprop > 0)
-        if (int rc = launch_proposals(h, origins, directions, nears, fars, height, width, opts, wp, g, ws, prop_depth_0, prop_depth_1, st, &d_ebins, psel, k2,
-                                      dump))
-            return rc;
+        if (int rc = launch_proposals(h, origins, directions, nears, fars, opts, plan, ws, prop_depth_0, prop_depth_1, st, psel, k2, dump)) return rc;
 
     SnMainParams p;
-    memset(&p, 0, sizeof(p));
-    p.origins = origins;
-    p.directions = directions;
-    p.nears = nears;
-    p.fars = fars;
-    p.sbins = d_sbins;
-    p.ebins = d_ebins;
-    p.spacing_uniform = opts->spacing_mode;
-    p.pm = h->pos_map;
+    fill_frame_params(p, h, origins, directions, nears, fars, *opts, plan);
+    p.sbins = opts->initial_spacing_bins;  // null => kernels fall back to i/N
+    if (nprop > 0) p.ebins = (float*)(ws + wp.off_ebins);
     p.table = (const float*)h->table_main.ptr;
     p.wimg = (const float*)(sel.split ? h->wimg_main_h.ptr : h->wimg_main.ptr);
     p.feat_scale = h->feat_scale_main;
@@ -1263,17 +1162,8 @@ static int render_rays_impl(SnHandle h, const float* origins, const float* direc
     p.chunk_minmax = d_minmax;
     p.n_chunks = wp.n_chunks;
     for (int l = 0; l < 16; ++l) p.scal[l] = d.main_field.scalings[l];
-    p.height = height;
-    p.width = width;
     p.n_samples = opts->num_nerf_samples;
-    p.tile_w_log2 = g.tw_log2;
-    p.tile_h_log2 = g.th_log2;
-    p.tiles_x = g.tiles_x;
-    p.tiles_y = g.tiles_y;
     p.log2_t = d.main_field.log2_hashmap_size;
-    p.near_plane = opts->near_plane;
-    p.far_plane = opts->far_plane;
-    p.avg_density = d.average_init_density;
     p.sh_remap = d.sh_remap;
     p.chunk_rays = opts->chunk_rays;
     p.bg_mode = opts->background_mode;
@@ -1287,29 +1177,18 @@ static int render_rays_impl(SnHandle h, const float* origins, const float* direc
         p.dump_q = dump->main_q;
         p.dump_median = dump->median_index;
     }
-    const int gbx = (g.tiles_x + 1) / 2, gby = (g.tiles_y + 1) / 2;
-    // weight image + (uniform sampler) the frame's S + 1 euclidean bins
-    const size_t etab_bytes = nprop == 0 ? ((size_t)opts->num_nerf_samples + 1 + 3) / 4 * 16 : 0;
-    const size_t lds_bytes = (sel.half1 ? (size_t)SnMainImgF16::TOTAL_BYTES : (size_t)SnMainImg::TOTAL * 4) + etab_bytes;
-    // split-depth tail (plan_tail): the workgroups of the last, partly filled round become n_seg segment jobs each
-    const bool tail_split = !dump && !sel.half1 && !h->sw.tail_split_off.load(std::memory_order_relaxed) && wp.n_seg > 1;
-    p.seg_first_block = gbx * gby;
-    p.n_seg = 1;
-    p.seg_len = opts->num_nerf_samples;
-    int n_tail = 0;
-    if (tail_split) {
-        n_tail = gbx * gby - wp.seg_first_block;
-        p.seg_first_block = wp.seg_first_block;
-        p.n_seg = wp.n_seg;
-        p.seg_len = wp.seg_len;
-        p.seg_scratch = (f32x4*)(ws + wp.off_seg);
-    }
-    const dim3 grid((unsigned)(gbx * gby - n_tail + ((n_tail + 7) / 8 * 8) * p.n_seg)), block(256);  // (segment jobs: the tail padded to whole XCD rows)
-    launch_kernel(k1, grid, block, lds_bytes, st, p);
+    // split-depth tail (sn_frame.h plan_tail): the workgroups of the last, partly filled round become n_seg segment jobs each
+    const SnMainLaunch ml = sn_main_launch(plan, sel.half1, nprop, dump != nullptr, h->sw.tail_split_off.load(std::memory_order_relaxed) != 0);
+    p.seg_first_block = ml.seg_first_block;
+    p.n_seg = ml.n_seg;
+    p.seg_len = ml.seg_len;
+    if (ml.n_tail) p.seg_scratch = (f32x4*)(ws + wp.off_seg);
+    const dim3 block(256);
+    launch_kernel(k1, dim3(ml.grid), block, ml.lds_bytes, st, p);
     SN_HIP(h, hipGetLastError());
-    if (tail_split) {
-        if (nprop > 0) hipLaunchKernelGGL((sn_main_combine_kernel<1>), dim3((unsigned)n_tail), block, 0, st, p);
-        else hipLaunchKernelGGL((sn_main_combine_kernel<0>), dim3((unsigned)n_tail), block, etab_bytes, st, p);
+    if (ml.n_tail) {
+        if (nprop > 0) hipLaunchKernelGGL((sn_main_combine_kernel<1>), dim3((unsigned)ml.n_tail), block, 0, st, p);
+        else hipLaunchKernelGGL((sn_main_combine_kernel<0>), dim3((unsigned)ml.n_tail), block, ml.etab_bytes, st, p);
         SN_HIP(h, hipGetLastError());
     }
     if (expected_depth) {
@@ -1430,21 +1309,13 @@ int sn_clock_probe(uint64_t* out, double seconds, SnStream stream) {
 
 int sn_render_normals(SnHandle h, const float* origins, const float* directions, const float* nears, const float* fars, int32_t height,
                       int32_t width, const SnRenderOpts* opts, float* normals, float* pred_normals, SnStream stream) {
-    if (!h) return SN_ERR_INVALID;
-    if (!origins || !directions || !opts || height <= 0 || width <= 0) return fail(h, SN_ERR_INVALID, "sn_render_normals: bad argument");
+    const char* who = "sn_render_normals";
     SnRenderOpts opts_own;
-    if (int rc = adopt_struct(h, opts, kRenderOptsMin, opts_own, "sn_render_normals: SnRenderOpts")) return rc;
+    SnFramePlan plan;
+    if (int rc = begin_render(who, h, origins, directions, nears, fars, height, width, opts, pred_normals != nullptr, opts_own)) return rc;
     opts = &opts_own;
-    if ((nears == nullptr) != (fars == nullptr)) return fail(h, SN_ERR_INVALID, "sn_render_normals: nears and fars must both be given or both be NULL");
-    if (!h->finalized) return fail(h, SN_ERR_STATE, "sn_render_normals: weights not finalized");
-    if (pred_normals && !h->has_pred_normals)
-        return fail(h, SN_ERR_STATE, "sn_render_normals: field.mlp_pred_normals.* / field.field_head_pred_normals.net.* not uploaded");
-    std::string why;
-    if (!valid_opts(h->desc, *opts, why)) return fail(h, SN_ERR_INVALID, "sn_render_normals: " + why);
     if (!normals && !pred_normals) return SN_OK;
-    const WorkspacePlan wp = plan_workspace(height, width, *opts, h->n_cus, true);
-    if (!opts->workspace || opts->workspace_bytes < wp.total)
-        return fail(h, SN_ERR_WORKSPACE, "sn_render_normals: workspace too small, need " + std::to_string(wp.total) + " bytes");
+    if (int rc = plan_render(who, h, height, width, *opts, plan)) return rc;
     // selected before anything is enqueued; the proposal kernel (and its refusals) only when this call samples its own bins
     const SnVariantFacts vf = variant_facts(h);
     const SnVariantRequest vr = variant_request(*opts, false);
@@ -1460,9 +1331,7 @@ int sn_render_normals(SnHandle h, const float* origins, const float* directions,
     RenderGuard guard(h, st);
     char* ws = (char*)opts->workspace;
     const SnFieldDesc& d = h->desc;
-    const TileGeom g = tile_geometry(height, width);
     const int nprop = opts->num_proposal_iterations;
-    float* d_ebins = nullptr;
     if (nprop > 0) {
         const WorkspaceStamp want = make_stamp(h, origins, directions, nears, fars, height, width, *opts);
         if (opts->reuse_final_bins) {
@@ -1470,55 +1339,36 @@ int sn_render_normals(SnHandle h, const float* origins, const float* directions,
             // what no stamp can see -- foreign writes to the memory, rays changed in place, device ordering -- stays the caller's word)
             const std::string why_not = stamp_mismatch(ws, want);
             if (!why_not.empty()) return fail(h, SN_ERR_STATE, "sn_render_normals: reuse_final_bins: " + why_not);
-            d_ebins = (float*)(ws + wp.off_ebins);
         } else {
             clear_stamp(ws);
-            if (int rc = launch_proposals(h, origins, directions, nears, fars, height, width, opts, wp, g, ws, nullptr, nullptr, st, &d_ebins, psel, k2))
-                return rc;
+            if (int rc = launch_proposals(h, origins, directions, nears, fars, opts, plan, ws, nullptr, nullptr, st, psel, k2)) return rc;
             stamp_workspace(ws, want);  // (the proposal kernel is deterministic: these ARE the bins a colour render of the same call would leave)
         }
     } else {
         clear_stamp(ws);
     }
     SnNormalsParams p;
-    memset(&p, 0, sizeof(p));
-    p.origins = origins;
-    p.directions = directions;
-    p.nears = nears;
-    p.fars = fars;
+    fill_frame_params(p, h, origins, directions, nears, fars, *opts, plan);
     p.sbins = opts->initial_spacing_bins;
-    p.ebins = d_ebins;
-    p.spacing_uniform = opts->spacing_mode;
-    p.pm = h->pos_map;
+    if (nprop > 0) p.ebins = (float*)(ws + plan.ws.off_ebins);
     p.table = (const float*)h->table_main.ptr;
     const bool split = sel.split;
     p.wimg = (const float*)(split ? h->wimg_normals_h.ptr : h->wimg_normals.ptr);
     p.normals = normals;
     p.pred_normals = pred_normals;
     for (int l = 0; l < 16; ++l) p.scal[l] = d.main_field.scalings[l];
-    p.height = height;
-    p.width = width;
     p.n_samples = opts->num_nerf_samples;
-    p.tile_w_log2 = g.tw_log2;
-    p.tile_h_log2 = g.th_log2;
-    p.tiles_x = g.tiles_x;
-    p.tiles_y = g.tiles_y;
     p.log2_t = d.main_field.log2_hashmap_size;
-    p.near_plane = opts->near_plane;
-    p.far_plane = opts->far_plane;
-    p.avg_density = d.average_init_density;
     p.grid = grid_levels(d.main_field);
     p.pe_rev_scale = d.main_field.grid_mode == 1 ? 0.5f : 1.0f;  // tiny-cuda-nn's Frequency encoding runs at pi 2^k
-    const int gbx = (g.tiles_x + 1) / 2, gby = (g.tiles_y + 1) / 2;
-    const size_t lds_bytes = split ? (size_t)SnNormImgH::TOTAL_BYTES : (size_t)SnNormImg::TOTAL * 4;
-    const dim3 grid((unsigned)(gbx * gby)), block(256);
+    const SnNormalsLaunch nl = sn_normals_launch(plan, split);
     if (sel.copies) {
         p.dense = h->dense_info;
         p.inv_feat_scale = 1.0f / h->feat_scale_main;
     }
     p.feat_scale = split ? h->feat_scale_main : 1.0f;
     p.grad_scale = split ? h->grad_scale_normals : 1.0f;
-    launch_kernel(k3, grid, block, lds_bytes, st, p);
+    launch_kernel(k3, dim3(nl.grid), dim3(256), nl.lds_bytes, st, p);
     SN_HIP(h, hipGetLastError());
     return SN_OK;
 }

@@ -1,5 +1,6 @@
 // sn_layout.h -- layout of the weight images the host packs (sn_weights.h) and the kernels read (sn_main.h, sn_normals.h,
-// sn_proposal.h).  Constants only, plain C++: included by device and host-only code alike.
+// sn_proposal.h), and the launch-shape constants the host plans with (sn_frame.h).  Constants only, plain C++: included by device and
+// host-only code alike.
 #pragma once
 
 // LDS weight image of the main field, float offsets.  Built on the host by sn_weights.h
@@ -75,3 +76,19 @@ struct SnNormImgH {
 // sum_r W1[r] b0[r] / 2 + b1
 #define SN_PROP_LIN 1236
 #define SN_PROP_PACK_FLOATS 1252
+
+// Launch shapes the host plans with (sn_frame.h) and the kernels are compiled for.
+// the occupancy the main kernel is compiled for (168 VGPRs): workgroups of 4 waves per CU
+#ifndef SN_MAIN_WAVES_PER_SIMD
+#define SN_MAIN_WAVES_PER_SIMD 3
+#endif
+#define SN_PROP_MAX_SAMPLES 256
+#define SN_PROP_WAVES 4
+#ifndef SN_PROP_WG_PER_CU
+#define SN_PROP_WG_PER_CU 3  // = waves per SIMD the kernel is compiled for (<= 168 VGPRs)
+#endif
+// per-wave scratch of the proposal kernel: weights [256][64] + two spacing-bin arrays [257][64]
+#define SN_PROP_SCRATCH_W 0
+#define SN_PROP_SCRATCH_B0 (SN_PROP_MAX_SAMPLES * 64)
+#define SN_PROP_SCRATCH_B1 (SN_PROP_SCRATCH_B0 + (SN_PROP_MAX_SAMPLES + 1) * 64)
+#define SN_PROP_SCRATCH_FLOATS (SN_PROP_SCRATCH_B1 + (SN_PROP_MAX_SAMPLES + 1) * 64)

@@ -620,15 +620,13 @@ SN_DEV void sn_main_field_f16(const char* __restrict__ ldsb, float* feat, const 
 // ------------------------------------------------------------------------------------------
 // kernel
 // ------------------------------------------------------------------------------------------
-// levels whose gathers are in flight together (64 VGPRs of loads at 4) and the occupancy the kernels are compiled for (168 VGPRs)
+// levels whose gathers are in flight together (64 VGPRs of loads at 4); the occupancy the kernels are compiled for (168 VGPRs) is
+// SN_MAIN_WAVES_PER_SIMD (sn_layout.h)
 #ifndef SN_FAST_HASH
 #define SN_FAST_HASH true  // fused kernels use the reduced-instruction hash arithmetic (sn_hash_corners_fast)
 #endif
 #ifndef SN_HASH_GROUP
 #define SN_HASH_GROUP 4
-#endif
-#ifndef SN_MAIN_WAVES_PER_SIMD
-#define SN_MAIN_WAVES_PER_SIMD 3
 #endif
 // how many of the leading de-hashed levels are kept in bilinear-coefficient form (sn_device.h SnDenseCopy::n_bc; 32 bytes per grid
 // point: levels 0-8 of the main grid are 0.51 GB, level 9 alone would add 0.82 GB) -- host and kernels read the same constants

@@ -18,14 +18,9 @@
 #pragma once
 #include "../../include/signerf_hip.h"
 #include "sn_device.h"
-#include "sn_layout.h"  // the proposal-net MLP pack: SN_PROP_W0 .. SN_PROP_PACK_FLOATS
+#include "sn_layout.h"  // the proposal-net MLP pack (SN_PROP_W0 .. SN_PROP_PACK_FLOATS); SN_PROP_MAX_SAMPLES, SN_PROP_WAVES, SN_PROP_WG_PER_CU, SN_PROP_SCRATCH_*
 #include "sn_main.h"  // fp16 hi+lo split helpers (sn_split2, f16x8)
 
-#define SN_PROP_MAX_SAMPLES 256
-#define SN_PROP_WAVES 4
-#ifndef SN_PROP_WG_PER_CU
-#define SN_PROP_WG_PER_CU 3  // = waves per SIMD the kernel is compiled for (<= 168 VGPRs)
-#endif
 // leading levels of a proposal net whose bilinear coefficients are kept in registers across the steps of the marching loop
 // (sn_device.h SnBcCache; 16 VGPRs per level).  Same-box A/B on the 1080p nerfacto frame (r02, tools/ab_lib.sh, 4 rounds of 40 frames;
 // K2 is ~57 % of the frame): no cache at 5 waves/SIMD (the previous configuration) 15.13 ms, no cache at 3 waves 15.38; 2 levels at
@@ -281,12 +276,6 @@ struct SnPropParams {
     int spacing_uniform;  // SnRenderOpts.spacing_mode (sn_spacing)
     SnPosMap pm;          // SnFieldDesc.disable_scene_contraction (sn_sample_q_fast)
 };
-
-// per-wave scratch: weights [256][64] + two spacing-bin arrays [257][64]
-#define SN_PROP_SCRATCH_W 0
-#define SN_PROP_SCRATCH_B0 (SN_PROP_MAX_SAMPLES * 64)
-#define SN_PROP_SCRATCH_B1 (SN_PROP_SCRATCH_B0 + (SN_PROP_MAX_SAMPLES + 1) * 64)
-#define SN_PROP_SCRATCH_FLOATS (SN_PROP_SCRATCH_B1 + (SN_PROP_MAX_SAMPLES + 1) * 64)
 
 // shared per-workgroup LDS: the sampler grids
 struct SnPropLds {

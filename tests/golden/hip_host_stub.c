@@ -65,7 +65,12 @@ int hipEventDestroy(void* e) { free(e); return 0; }
 int hipEventRecord(void* e, void* s) { (void)e; (void)s; return 0; }
 int hipEventSynchronize(void* e) { (void)e; return 0; }
 int hipGetDevice(int* d) { *d = 0; return 0; }
-int hipDeviceGetAttribute(int* v, int a, int d) { (void)a; (void)d; *v = 256; return 0; }
+int hipDeviceGetAttribute(int* v, int a, int d) {   // every attribute, the CU count among them: HIP_STUB_CUS, or 256
+    (void)a; (void)d;
+    const char* e = getenv("HIP_STUB_CUS");
+    *v = e ? atoi(e) : 256;
+    return 0;
+}
 const char* hipGetErrorString(int e) { (void)e; return "stub"; }
 int hipGetLastError(void) { return 0; }
 

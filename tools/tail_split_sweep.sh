@@ -1,5 +1,5 @@
 #!/bin/bash
-# Split-depth tail of K1 (sn_api.hip plan_tail) on / off over frame sizes, frames issued back to back on one stream (steady clocks; a frame
+# Split-depth tail of K1 (sn_frame.h plan_tail) on / off over frame sizes, frames issued back to back on one stream (steady clocks; a frame
 # timed on its own after an idle gap runs at whatever the power state happens to be):   tools/tail_split_sweep.sh [sizes...]
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 for s in "${@:-64 128 200 256 320 400 512 560 640 800 1024}"; do
