@@ -1178,6 +1178,28 @@ SN_DEV void sn_aabb_slab(const float* __restrict__ o3, const float* __restrict__
     fars = nan ? __uint_as_float(0x7fc00000u) : fr;
 }
 
+// The clamped slab test of nerfstudio's intersect_aabb (generate_rays(aabb_box=...), and intersect_obb in the box's frame) from the six
+// plane distances a[c] = (min_c - o_c) / d_c, b[c] = (max_c - o_c) / d_c: near = max over the axes of min(a, b), far = min over the axes
+// of max(a, b), both clamped to [0, 1e10]; far <= near -> 1e10 for both.  nerfstudio forms them with amin / amax / clamp, which all hand a
+// NaN on, as above: any NaN among the six distances makes both results NaN.  A NaN comes from a non-finite origin, direction or box
+// entry, and from 0 / 0 when d_c == 0 and the origin lies on a box plane -- an axis-aligned camera whose pixel centre is on the principal
+// point.  Finite distances take the fminf / fmaxf path alone.
+SN_DEV void sn_clamped_slab(const float a[3], const float b[3], float& tnear, float& tfar) {
+    float tmin = -INFINITY, tmax = INFINITY;
+    bool nan = false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        nan = nan || (a[c] != a[c]) || (b[c] != b[c]);
+        tmin = fmaxf(tmin, fminf(a[c], b[c]));
+        tmax = fminf(tmax, fmaxf(a[c], b[c]));
+    }
+    tmin = fminf(fmaxf(tmin, 0.0f), 1e10f);
+    tmax = fminf(fmaxf(tmax, 0.0f), 1e10f);
+    if (tmax <= tmin) tmin = tmax = 1e10f;
+    tnear = nan ? __uint_as_float(0x7fc00000u) : tmin;
+    tfar = nan ? __uint_as_float(0x7fc00000u) : tmax;
+}
+
 // ReLU as ONE integer max on the bit pattern (hipcc turns fmaxf(x, 0) on an MFMA result into TWO v_max_f32, a canonicalising
 // one first, and folds v_med3(x, 0, inf) back into the same pair): negative floats are negative ints, -0.0 is INT_MIN, positive
 // floats keep their bits.  NaN handling is restored separately where it matters (sn_main.h).

@@ -84,7 +84,8 @@ SN_DEV void sn_cam_dir(const float* c2w, float u, float v, float out[3], float& 
     float n = sqrtf((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
     // nerfstudio's camera_utils.normalize_with_norm floors the norm at its module constant _EPS = np.finfo(float).eps * 4 (8.88e-16 [NS-RECALL, M-H];
     // r01-r04 used 1e-20): it only matters for a direction shorter than that -- a degenerate camera matrix -- and the fixture decides it by data
-    n = fmaxf(n, 8.8817841970012523e-16f);
+    // torch.maximum hands a NaN norm on (a NaN in the rotation, the fisheye ray through the principal point: 0 / 0), fmaxf would floor it
+    n = n < 8.8817841970012523e-16f ? 8.8817841970012523e-16f : n;
 #pragma unroll
     for (int i = 0; i < 3; ++i) out[i] = w[i] / n;
     norm = n;
@@ -92,7 +93,7 @@ SN_DEV void sn_cam_dir(const float* c2w, float u, float v, float out[3], float& 
 
 // One ray of one camera from its image coordinates (y, x): what sn_generate_rays_kernel computes per pixel and sn_ray_batch_kernel
 // (sn_ray_batch.h) per (camera, y, x) triplet -- the ONE copy of this arithmetic, so the two kernels agree to the bit.  `area` is
-// computed with want_area, `tnear` / `tfar` with want_box (nerfstudio intersect_aabb: clamped slab test, invalid -> 1e10, A1).
+// computed with want_area, `tnear` / `tfar` with want_box (nerfstudio intersect_aabb: sn_clamped_slab, invalid -> 1e10, a NaN plane distance -> NaN, A1).
 struct SnRay {
     float o[3], d[3];
     float area, norm, tnear, tfar;
@@ -129,22 +130,13 @@ SN_DEV void sn_camera_ray(const float* c2w, float fx, float fy, float cx, float 
         r.area = sqrtf(a) * sqrtf(b);
     }
     if (want_box) {
-        float tmin = -INFINITY, tmax = INFINITY;
+        float a[3], b[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            float a = (aabb[c] - r.o[c]) / r.d[c];
-            float b = (aabb[3 + c] - r.o[c]) / r.d[c];
-            tmin = fmaxf(tmin, fminf(a, b));
-            tmax = fminf(tmax, fmaxf(a, b));
+            a[c] = (aabb[c] - r.o[c]) / r.d[c];
+            b[c] = (aabb[3 + c] - r.o[c]) / r.d[c];
         }
-        tmin = fminf(fmaxf(tmin, 0.0f), 1e10f);
-        tmax = fminf(fmaxf(tmax, 0.0f), 1e10f);
-        if (tmax <= tmin) {
-            tmin = 1e10f;
-            tmax = 1e10f;
-        }
-        r.tnear = tmin;
-        r.tfar = tmax;
+        sn_clamped_slab(a, b, r.tnear, r.tfar);
     }
 }
 
@@ -207,7 +199,7 @@ __global__ void sn_intersect_with_aabb_kernel(const float* origins, const float*
 
 // ------------------------------------------------------------------------------------------
 // viewer crop: nerfstudio's intersect_obb [NS] -- rays into the box frame (world2box = inverse of [R | T]),
-// then the clamped slab test of intersect_aabb against [-S/2, S/2]; invalid -> 1e10 for both
+// then the clamped slab test of intersect_aabb (sn_clamped_slab) against [-S/2, S/2]; invalid -> 1e10 for both
 // ------------------------------------------------------------------------------------------
 struct SnObb {
     float w2b[12];  // 3x4 row-major
@@ -220,19 +212,17 @@ __global__ void sn_intersect_obb_kernel(const float* origins, const float* direc
     if (i >= n) return;
     const float o[3] = {origins[i * 3], origins[i * 3 + 1], origins[i * 3 + 2]};
     const float d[3] = {directions[i * 3], directions[i * 3 + 1], directions[i * 3 + 2]};
-    float tmin = -INFINITY, tmax = INFINITY;
+    float a[3], b[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float* m = box.w2b + 4 * c;
         const float ob = ((m[0] * o[0] + m[1] * o[1]) + m[2] * o[2]) + m[3];
         const float db = (m[0] * d[0] + m[1] * d[1]) + m[2] * d[2];
-        const float a = (-box.half[c] - ob) / db, b = (box.half[c] - ob) / db;
-        tmin = fmaxf(tmin, fminf(a, b));
-        tmax = fminf(tmax, fmaxf(a, b));
+        a[c] = (-box.half[c] - ob) / db;
+        b[c] = (box.half[c] - ob) / db;
     }
-    tmin = fminf(fmaxf(tmin, 0.0f), 1e10f);
-    tmax = fminf(fmaxf(tmax, 0.0f), 1e10f);
-    if (tmax <= tmin) tmin = tmax = 1e10f;
+    float tmin, tmax;
+    sn_clamped_slab(a, b, tmin, tmax);
     nears[i] = tmin;
     fars[i] = tmax;
 }

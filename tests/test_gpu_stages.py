@@ -44,9 +44,11 @@ def test_generate_rays(gpu, H, W, cam):
     # the SIGNeRF call site passes camera_indices=0 on a 0-dim camera (datasetgenerator.py:691): indices are all 0
     assert int(b.camera_indices.max()) == 0 and int(b.camera_indices.min()) == 0 and b.camera_indices.dtype == torch.int64
     d = b.directions.cpu()
-    assert float((d - ref["directions"]).abs().max()) <= 2e-7               # fp32 ulp-level
+    # the kernel IS the written fp32 arithmetic to the bit (tests/test_gpu_ray_edges.py), which differs from the oracle by the accumulation
+    # order inside the norm alone: one ulp of the norm, one rounding of the quotient (tests/test_ray_oracle_host.py)
+    assert float((d - ref["directions"]).abs().max()) <= 1.2e-7
     assert float(((b.pixel_area.cpu() - ref["pixel_area"]).abs() / ref["pixel_area"]).max()) <= 1e-3
-    assert float((b.metadata["directions_norm"].cpu() - ref["directions_norm"]).abs().max()) <= 1e-6
+    assert float((b.metadata["directions_norm"].cpu() - ref["directions_norm"]).abs().max()) <= 1.2e-7    # one ulp of a norm in [1, 2)
     # ray index <-> (y, x): pixel (y, x) must hold the direction through pixel centre (x+.5, y+.5) -- exact index map
     y, x = H // 3, (2 * W) // 3
     cam_dir = torch.tensor([(x + 0.5 - cx) / fx, -(y + 0.5 - cy) / fy, -1.0])
@@ -61,8 +63,8 @@ def test_generate_rays_with_aabb(gpu):
     b = cams[2].generate_rays(camera_indices=0, aabb_box=box)
     ref = onf.generate_rays(c2w[2, :3], 60.0, 60.0, 24.0, 24.0, 48, 48)
     tmin, tmax = onf.intersect_aabb_ns(b.origins.cpu().reshape(-1, 3), b.directions.cpu().reshape(-1, 3), box.aabb.flatten())
-    assert torch.allclose(b.nears.cpu().reshape(-1), tmin, rtol=1e-6, atol=1e-6)
-    assert torch.allclose(b.fars.cpu().reshape(-1), tmax, rtol=1e-6, atol=1e-6)
+    assert torch.equal(b.nears.cpu().reshape(-1), tmin)      # given the same rays the clamped slab test is the oracle's to the bit
+    assert torch.equal(b.fars.cpu().reshape(-1), tmax)
     assert float((b.nears == 1e10).float().mean()) > 0.05  # some rays miss the box -> sentinel
 
 
