@@ -95,7 +95,8 @@ typedef struct SnHashMlpDesc {
     int32_t num_levels;         /* L */
     int32_t features_per_level; /* F, must be 2 */
     int32_t log2_hashmap_size;  /* table rows per level = 1 << this */
-    int32_t hidden_dim;         /* 64 for the main field, 16 for proposal nets */
+    int32_t hidden_dim;         /* main field: 64, or 128 (a WIDE field, with hidden_dim_color 128: exact fp32 only, no normals /
+                                   instrumented / counting kernels -- those calls return SN_ERR_INVALID); 16 for proposal nets */
     int32_t num_layers;         /* must be 2 (one hidden layer) */
     int32_t out_dim;            /* 16 (1 + geo_feat_dim) main, 1 proposal */
     float scalings[SN_MAX_LEVELS]; /* grid_mode 0: floor(base_res * growth**l), computed by the host exactly as HashEncoding does;
@@ -112,7 +113,7 @@ typedef struct SnFieldDesc {
     uint32_t struct_size;         /* sizeof(SnFieldDesc) in the caller's header ("ABI evolution" above) */
     SnHashMlpDesc main_field;
     int32_t geo_feat_dim;         /* 15 */
-    int32_t hidden_dim_color;     /* 64 */
+    int32_t hidden_dim_color;     /* = main_field.hidden_dim: 64 or 128; the pairs (64, 64) and (128, 128) are built, no other */
     int32_t appearance_embed_dim; /* 32 (folded into the colour bias at finalize) */
     int32_t sh_levels;            /* 4 */
     int32_t sh_remap;             /* 0: SH evaluated on (d+1)/2 (torch fallback); 1: on d (tcnn) */

@@ -38,7 +38,11 @@ class NerfactoModelConfig(InstantiateConfig):
     far_plane: float = 1000.0
     background_color: str = "last_sample"
     hidden_dim: int = 64
+    """Width of the density MLP.  The kernels are built for (hidden_dim, hidden_dim_color) = (64, 64), nerfacto's default, and
+    (128, 128), the WIDE field of nerfstudio's ``nerfacto-big``; any other pair is refused by the library.  A wide field renders in
+    exact fp32 whatever ``precision`` asks for (``effective_precision`` says "fp32") and has no normals kernel (DESIGN.md §4 "Wide fields")."""
     hidden_dim_color: int = 64
+    """Width of the colour MLP: equal to ``hidden_dim`` (64 or 128)."""
     num_levels: int = 16
     base_res: int = 16
     max_res: int = 2048

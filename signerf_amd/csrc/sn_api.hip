@@ -8,6 +8,7 @@
 #include "../../include/signerf_hip_ray_batch.h"
 
 #include <hip/hip_runtime.h>
+#include <dlfcn.h>
 
 #include <cmath>
 #include <cstdio>
@@ -35,6 +36,8 @@
 #include "sn_ray_batch.h"
 #include "sn_variant.h"
 #include "sn_weights.h"
+#include "sn_wide.h"
+#include "sn_wide_kernels.h"
 
 namespace {
 
@@ -90,6 +93,8 @@ struct SnContext {
     std::string split_why;
     bool normals_split_ok = true;  // the normals kernel's own conditioned operands fit fp16 (sn_finalize_weights)
     float grad_scale_normals = 1.0f;  // power of two carried by the split-precision reverse-pass layer of the normals kernel
+    bool wide = false;           // hidden_dim = hidden_dim_color = 128: the wide kernels (sn_wide.h, sn_wide_kernels.h), exact fp32 only
+    bool wide_lds_raised = false;  // the wide kernels' dynamic-LDS limit was raised on this handle's device (hipFuncSetAttribute)
     bool finalized = false;
     std::atomic<uint64_t> weights_epoch{0};  // advanced by every sn_upload_weights / sn_finalize_weights (the workspace stamps carry it)
     uint64_t id = 0;                         // process-unique handle number (a stamp must not match a NEW handle at a recycled address)
@@ -625,6 +630,48 @@ const KernelEntry<SnPropVariant, SnPropParams> kPropKernels[] = {SN_PROP_VARIANT
 const KernelEntry<SnNormalsVariant, SnNormalsParams> kNormalsKernels[] = {SN_NORMALS_VARIANTS(SN_X)};
 #undef SN_X
 
+#define SN_X(...) {{__VA_ARGS__}, &sn_wide_field_main_kernel<__VA_ARGS__>},
+const KernelEntry<SnWideMainVariant, SnMainParams> kWideMainKernels[] = {SN_WIDE_MAIN_VARIANTS(SN_X)};
+#undef SN_X
+
+// The wide kernels keep ~115 KiB of weights in LDS: dynamic LDS above 64 KiB must be allowed per kernel before the first launch.  Made on a
+// wide handle's path only (a default handle never calls it).
+// The runtime call is looked up by name instead of being linked: the CPU-side launch tests (tests/test_launch_variants_host.py,
+// tests/test_frame_plan_host.py, tests/test_weights_host.py) load this library against tests/golden/hip_host_stub.c, a stand-in
+// libamdhip64.so.7 that does not provide hipFuncSetAttribute, and ctypes binds every symbol at load time (RTLD_NOW) -- a link-time
+// reference would keep the library from loading there at all.  Looked up in the runtime that serves hipGetDevice, so a process with one
+// HIP runtime calls that runtime's function.  The flag is per handle (the attribute belongs to kernel and device): a second wide handle
+// repeats the five calls once, which is harmless.
+int raise_wide_lds_limit(SnHandle h) {
+    std::lock_guard<std::mutex> g(h->mu);
+    if (h->wide_lds_raised) return SN_OK;
+    typedef hipError_t (*SetAttrFn)(const void*, hipFuncAttribute, int);
+    static const SetAttrFn set_attr = [] {
+        // in the HIP runtime this library is bound to (the one that serves hipGetDevice), wherever the process keeps it
+        void* sym = nullptr;
+        Dl_info info;
+        if (dladdr((const void*)&hipGetDevice, &info) && info.dli_fname)
+            if (void* rt = dlopen(info.dli_fname, RTLD_NOLOAD | RTLD_LAZY)) sym = dlsym(rt, "hipFuncSetAttribute");
+        if (!sym) sym = dlsym(RTLD_DEFAULT, "hipFuncSetAttribute");
+        return (SetAttrFn)sym;
+    }();
+    if (!set_attr) {
+        h->error = "wide field: this HIP runtime has no hipFuncSetAttribute (needed for more than 64 KiB of dynamic LDS)";
+        return SN_ERR_HIP;
+    }
+    for (const auto& e : kWideMainKernels)
+        if (set_attr((const void*)e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSnWideMaxLdsBytes) != hipSuccess) {
+            h->error = "wide field: the device refuses " + std::to_string(kSnWideMaxLdsBytes) + " bytes of dynamic LDS per workgroup";
+            return SN_ERR_HIP;
+        }
+    if (set_attr((const void*)&sn_wide_field_stage_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SnWideImg::TOTAL * 4)) != hipSuccess) {
+        h->error = "wide field: the device refuses the dynamic LDS of the wide stage kernel";
+        return SN_ERR_HIP;
+    }
+    h->wide_lds_raised = true;
+    return SN_OK;
+}
+
 // selection -> kernel.  A refusal is returned as it is; a selection that is not built is a bug in sn_variant.h: an error, never another kernel.
 template <typename V, typename P, size_t N>
 int pick_kernel(SnHandle h, const SnSelection<V>& sel, const KernelEntry<V, P> (&table)[N], const char* kernel, void (*&fn)(P)) {
@@ -701,9 +748,14 @@ int sn_create(const SnFieldDesc* desc_in, SnHandle* out) {
     if (int rc = adopt_struct(nullptr, desc_in, kFieldDescMin, desc_own, "sn_create: SnFieldDesc")) return rc;
     const SnFieldDesc* desc = &desc_own;
     std::string why;
-    if (!check_hashmlp(desc->main_field, 16, 64, 16, why)) return fail(nullptr, SN_ERR_INVALID, "main field: " + why);
-    if (desc->geo_feat_dim != 15 || desc->hidden_dim_color != 64 || desc->sh_levels != 4)
-        return fail(nullptr, SN_ERR_INVALID, "unsupported colour head: need geo_feat_dim 15, hidden_dim_color 64, sh_levels 4");
+    // two field widths are built: nerfacto's default (64, 64) and the wide field (128, 128) of nerfacto-big (sn_wide.h)
+    const bool wide = sn_is_wide(*desc);
+    if (!check_hashmlp(desc->main_field, 16, wide ? SnWideImg::HIDDEN : 64, 16, why))
+        return fail(nullptr, SN_ERR_INVALID, "main field: " + why + (why.rfind("hidden_dim", 0) == 0 ? std::string(" -- ") + kSnWidthPairsText : std::string()));
+    if (!sn_width_pair_supported(desc->main_field.hidden_dim, desc->hidden_dim_color))
+        return fail(nullptr, SN_ERR_INVALID, std::string("unsupported colour head: hidden_dim_color must equal hidden_dim -- ") + kSnWidthPairsText);
+    if (desc->geo_feat_dim != 15 || desc->sh_levels != 4)
+        return fail(nullptr, SN_ERR_INVALID, "unsupported colour head: need geo_feat_dim 15, sh_levels 4");
     if (desc->appearance_embed_dim < 0 || desc->appearance_embed_dim > 256)
         return fail(nullptr, SN_ERR_INVALID, "appearance_embed_dim out of range");
     if (desc->num_proposals < 0 || desc->num_proposals > SN_MAX_PROPOSALS)
@@ -719,6 +771,7 @@ int sn_create(const SnFieldDesc* desc_in, SnHandle* out) {
                 return fail(nullptr, SN_ERR_INVALID, "disable_scene_contraction needs a scene box with positive finite extents (SnFieldDesc.aabb)");
     SnContext* c = new SnContext();
     c->desc = *desc;
+    c->wide = wide;
     c->pos_map.box = desc->disable_scene_contraction;
     for (int k = 0; k < 3; ++k) {
         const float len = desc->disable_scene_contraction ? desc->aabb[3 + k] - desc->aabb[k] : 1.0f;  // (aabb[1] - aabb[0] in fp32, as SceneBox does)
@@ -834,12 +887,14 @@ int sn_finalize_weights(SnHandle h, SnStream stream) {
         size_t count;
         const std::vector<float>* SnMainTensors::*slot;
     };
+    const bool wide = h->wide;
+    const size_t HD = wide ? SnWideImg::HIDDEN : 64;  // width of the main field's hidden layers (sn_create: both MLPs have the same)
     const Need needs[] = {
-        {"field.mlp_base.mlp.layers.0.weight", 64 * 32, &SnMainTensors::W1},       {"field.mlp_base.mlp.layers.0.bias", 64, &SnMainTensors::b1},
-        {"field.mlp_base.mlp.layers.1.weight", 16 * 64, &SnMainTensors::W2},       {"field.mlp_base.mlp.layers.1.bias", 16, &SnMainTensors::b2},
-        {"field.mlp_head.layers.0.weight", (size_t)64 * cin, &SnMainTensors::Wc1}, {"field.mlp_head.layers.0.bias", 64, &SnMainTensors::bc1},
-        {"field.mlp_head.layers.1.weight", 64 * 64, &SnMainTensors::Wc2},          {"field.mlp_head.layers.1.bias", 64, &SnMainTensors::bc2},
-        {"field.mlp_head.layers.2.weight", 3 * 64, &SnMainTensors::Wc3},           {"field.mlp_head.layers.2.bias", 3, &SnMainTensors::bc3},
+        {"field.mlp_base.mlp.layers.0.weight", HD * 32, &SnMainTensors::W1},   {"field.mlp_base.mlp.layers.0.bias", HD, &SnMainTensors::b1},
+        {"field.mlp_base.mlp.layers.1.weight", 16 * HD, &SnMainTensors::W2},   {"field.mlp_base.mlp.layers.1.bias", 16, &SnMainTensors::b2},
+        {"field.mlp_head.layers.0.weight", HD * cin, &SnMainTensors::Wc1},     {"field.mlp_head.layers.0.bias", HD, &SnMainTensors::bc1},
+        {"field.mlp_head.layers.1.weight", HD * HD, &SnMainTensors::Wc2},      {"field.mlp_head.layers.1.bias", HD, &SnMainTensors::bc2},
+        {"field.mlp_head.layers.2.weight", 3 * HD, &SnMainTensors::Wc3},       {"field.mlp_head.layers.2.bias", 3, &SnMainTensors::bc3},
     };
     SnMainTensors mt{};
     for (const Need& n : needs) {
@@ -874,22 +929,31 @@ int sn_finalize_weights(SnHandle h, SnStream stream) {
     h->table_absmax_main = absmax_main;
 
     // the images and the scalars the handle keeps: host arithmetic alone (sn_weights.h).  They stay alive until the stream is synchronised.
-    const SnMainImages main = pack_main_images(d, mt, absmax_main);
-    const SnNormalImages norm = pack_normal_images(d, mt, main, nt);
+    // A wide field has ONE image, exact fp32 (sn_weights.h build_wide_image): no split-precision form, no normals images, no feature scale.
+    const SnMainImages main = wide ? SnMainImages{} : pack_main_images(d, mt, absmax_main);
+    const SnNormalImages norm = wide ? SnNormalImages{} : pack_normal_images(d, mt, main, nt);
+    const std::vector<float> wide_img = wide ? pack_wide_image(d, mt) : std::vector<float>();
     SnPropPack prop[SN_MAX_PROPOSALS];
     for (int i = 0; i < d.num_proposals; ++i) prop[i] = pack_proposal(*pt[i][0], *pt[i][1], *pt[i][2], *pt[i][3], absmax_prop[i]);
-    h->feat_scale_main = main.plan.t0;
-    h->split_ok = main.split_ok;
-    h->split_why = main.split_why;
-    h->has_pred_normals = norm.has_pred_normals;
-    h->normals_split_ok = norm.normals_split_ok;
+    h->feat_scale_main = wide ? 1.0f : main.plan.t0;
+    h->split_ok = wide ? false : main.split_ok;
+    h->split_why = wide ? std::string("wide field: exact fp32 only") : main.split_why;
+    h->has_pred_normals = wide ? false : norm.has_pred_normals;
+    h->normals_split_ok = wide ? false : norm.normals_split_ok;
     h->grad_scale_normals = norm.grad_scale_normals;
     for (int i = 0; i < d.num_proposals; ++i) h->feat_scale_prop[i] = prop[i].t0p;
 
-    if (int rc = upload_image(h, h->wimg_main, main.img, st)) return rc;
-    if (int rc = upload_image(h, h->wimg_main_h, main.imgh, st)) return rc;
-    if (int rc = upload_image(h, h->wimg_normals, norm.nimg, st)) return rc;
-    if (int rc = upload_image(h, h->wimg_normals_h, norm.nh, st)) return rc;
+    if (wide) {
+        if (int rc = upload_image(h, h->wimg_main, wide_img, st)) return rc;
+        h->wimg_main_h.release();
+        h->wimg_normals.release();
+        h->wimg_normals_h.release();
+    } else {
+        if (int rc = upload_image(h, h->wimg_main, main.img, st)) return rc;
+        if (int rc = upload_image(h, h->wimg_main_h, main.imgh, st)) return rc;
+        if (int rc = upload_image(h, h->wimg_normals, norm.nimg, st)) return rc;
+        if (int rc = upload_image(h, h->wimg_normals_h, norm.nh, st)) return rc;
+    }
     for (int i = 0; i < d.num_proposals; ++i)
         if (int rc = upload_image(h, h->wpack_prop[i], prop[i].pack, st)) return rc;
     // de-hashed copies of the coarse levels
@@ -900,7 +964,7 @@ int sn_finalize_weights(SnHandle h, SnStream stream) {
         const int asked = d.dense_levels == 0 ? SN_DENSE_LEVELS_DEFAULT : std::max(0, d.dense_levels);
         const int want = std::max(0, std::min(asked, 12));
         const uint64_t cap_main = d.dense_copy_cap_mb > 0 ? (uint64_t)d.dense_copy_cap_mb : 600;
-        int want_main = dense_levels_under_cap(d.main_field, want, cap_main);
+        int want_main = wide ? 0 : dense_levels_under_cap(d.main_field, want, cap_main);  // (a wide handle reads the uploaded table only: dense_levels is ignored)
         want_main = want_main >= SN_DENSE_LEVELS_DEFAULT ? SN_DENSE_LEVELS_DEFAULT : (want_main >= SN_BC_MAIN ? SN_BC_MAIN : 0);
         if (int rc = build_dense_copies(h, d.main_field, h->table_main, want_main, cap_main, h->dense_main, h->dense_info, h->dense_res, h->nd_torch, st,
                                         SN_BC_MAIN, h->feat_scale_main))
@@ -912,7 +976,7 @@ int sn_finalize_weights(SnHandle h, SnStream stream) {
         // single-fp16 mode: the main grid once more in fp16 storage (tiny-cuda-nn grids whose copies cover the densely indexed levels)
         const char* hg = getenv("SN_HALF_GRID");   // (diagnostics: 0 forces the fp32-table path of the mode)
         const int td = d.main_field.grid_mode == 1 ? leading_dense(d.main_field) : -1;
-        if (d.half_grid == 1 && !(hg && atoi(hg) == 0) && d.main_field.grid_mode == 1 && h->split_ok && h->nd_torch > 0 && td >= 0 && td <= h->nd_torch) {
+        if (!wide && d.half_grid == 1 && !(hg && atoi(hg) == 0) && d.main_field.grid_mode == 1 && h->split_ok && h->nd_torch > 0 && td >= 0 && td <= h->nd_torch) {
             if (int rc = build_half_grid(h, d.main_field, h->table_main, h->dense_info, h->nd_torch, h->hquads_main, h->hquads_info, h->hrows_main, h->hpinfo_main,
                                          st, h->feat_scale_main, h->table_absmax_main))
                 return rc;
@@ -924,7 +988,7 @@ int sn_finalize_weights(SnHandle h, SnStream stream) {
     }
 #if SN_MAIN_PAIRS
     // main grid, torch semantics: the levels beyond the de-hashed ones from x-paired tables (4 gathers per level instead of 8)
-    if (h->nd_torch > 0 && d.num_proposals > 0) {  // read by the bins-mode kernel only (sn_main.h)
+    if (!wide && h->nd_torch > 0 && d.num_proposals > 0) {  // read by the bins-mode kernel only (sn_main.h)
         if (int rc = build_pairs(h, d.main_field, h->table_main, h->pairs_main, h->pinfo_main, st, h->feat_scale_main, h->nd_torch)) return rc;
     } else {
         h->pairs_main.release();
@@ -1114,11 +1178,17 @@ static int render_rays_impl(SnHandle h, const float* origins, const float* direc
     // call must not return SN_ERR_INVALID with the proposal kernel already enqueued and its counters half updated)
     const SnVariantFacts vf = variant_facts(h);
     const SnVariantRequest vr = variant_request(*opts, dump != nullptr);
-    const SnMainSelection sel = sn_select_main(vf, vr);  // (with proposal iterations: the proposal kernel's refusals too)
+    // a wide handle selects among its own four instantiations (sn_wide.h); `sel` then only carries the launcher flags (all off)
+    const bool wide = h->wide;
+    const SnWideMainSelection wsel = wide ? sn_select_main_wide(vf, vr) : SnWideMainSelection{};
+    const SnMainSelection sel = wide ? SnMainSelection{} : sn_select_main(vf, vr);  // (with proposal iterations: the proposal kernel's refusals too)
     const SnPropSelection psel = sn_select_proposal(vf, vr);
     void (*k1)(SnMainParams) = nullptr;
     void (*k2)(SnPropParams) = nullptr;
-    if (int rc = pick_kernel(h, sel, kMainKernels, "sn_render_main_kernel", k1)) return rc;
+    if (wide) {
+        if (int rc = pick_kernel(h, wsel, kWideMainKernels, "sn_wide_field_main_kernel", k1)) return rc;
+        if (int rc = raise_wide_lds_limit(h)) return rc;
+    } else if (int rc = pick_kernel(h, sel, kMainKernels, "sn_render_main_kernel", k1)) return rc;
     if (vr.num_proposal_iterations > 0)
         if (int rc = pick_kernel(h, psel, kPropKernels, "sn_proposal_kernel", k2)) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -1178,7 +1248,12 @@ static int render_rays_impl(SnHandle h, const float* origins, const float* direc
         p.dump_median = dump->median_index;
     }
     // split-depth tail (sn_frame.h plan_tail): the workgroups of the last, partly filled round become n_seg segment jobs each
-    const SnMainLaunch ml = sn_main_launch(plan, sel.half1, nprop, dump != nullptr, h->sw.tail_split_off.load(std::memory_order_relaxed) != 0);
+    SnMainLaunch ml = sn_main_launch(plan, sel.half1, nprop, dump != nullptr, wide || h->sw.tail_split_off.load(std::memory_order_relaxed) != 0);
+    if (wide) {  // whole-ray workgroups only; the wide image + bins in LDS
+        const SnWideLaunch wl = sn_wide_main_launch(plan, nprop);
+        ml.grid = wl.grid;
+        ml.lds_bytes = wl.lds_bytes;
+    }
     p.seg_first_block = ml.seg_first_block;
     p.n_seg = ml.n_seg;
     p.seg_len = ml.seg_len;
@@ -1217,6 +1292,7 @@ int sn_render_rays_debug(SnHandle h, const float* origins, const float* directio
 
 int sn_effective_precision(SnHandle h, int32_t requested, int32_t kernel) {
     if (!h || !h->finalized) return -1;
+    if (h->wide) return sn_effective_precision_wide(variant_facts(h), requested, kernel);
     return sn_effective_precision_of(variant_facts(h), requested, kernel);
 }
 
@@ -1312,6 +1388,7 @@ int sn_render_normals(SnHandle h, const float* origins, const float* directions,
     const char* who = "sn_render_normals";
     SnRenderOpts opts_own;
     SnFramePlan plan;
+    if (h && h->wide) return fail(h, SN_ERR_INVALID, kSnWideNoNormals);  // (before anything else: a wide handle keeps no pred-normal MLP either)
     if (int rc = begin_render(who, h, origins, directions, nears, fars, height, width, opts, pred_normals != nullptr, opts_own)) return rc;
     opts = &opts_own;
     if (!normals && !pred_normals) return SN_OK;
@@ -1419,6 +1496,7 @@ int sn_field_forward_geo(SnHandle h, int32_t which, const float* positions, cons
     if (precision < 0 || precision > 2) return fail(h, SN_ERR_INVALID, "sn_field_forward: precision must be 0, 1 or 2");
     if (precision == 2 && h->desc.main_field.grid_mode != 1)
         return fail(h, SN_ERR_INVALID, "precision 2 (single fp16) is the arithmetic of tiny-cuda-nn checkpoints: grid_mode 1 only");
+    if (which < 0 && h->wide && precision == 2) return fail(h, SN_ERR_INVALID, std::string("sn_field_forward: ") + kSnWideNoHalf);
     if (n == 0) return SN_OK;
     hipStream_t st = (hipStream_t)stream;
     if (which < 0) {
@@ -1440,7 +1518,11 @@ int sn_field_forward_geo(SnHandle h, int32_t which, const float* positions, cons
         p.geo = geo;
         p.grid_mode = h->desc.main_field.grid_mode;
         p.grid = grid_levels(h->desc.main_field);
-        if (precision == 0)
+        if (h->wide) {  // exact fp32 whatever was asked for; one workgroup per CU (the image fills its LDS), blocks of 256 points in a grid-stride loop
+            if (int rc = raise_wide_lds_limit(h)) return rc;
+            const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, std::max(h->n_cus, 1));
+            hipLaunchKernelGGL(sn_wide_field_stage_kernel, dim3(grid), dim3(256), (size_t)SnWideImg::TOTAL * 4, st, p);
+        } else if (precision == 0)
             hipLaunchKernelGGL(sn_main_field_stage_kernel<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), (size_t)SnMainImg::TOTAL * 4, st, p);
         else if (precision == 2)
             hipLaunchKernelGGL(sn_main_field_stage_kernel<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), (size_t)SnMainImgF16::TOTAL_BYTES, st, p);

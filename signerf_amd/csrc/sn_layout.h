@@ -20,6 +20,27 @@ struct SnMainImg {
     static constexpr int TOTAL = B3 + 4;  // 10 660 floats = 42 640 bytes; a multiple of 4
 };
 
+// LDS weight image of a WIDE main field (hidden_dim = hidden_dim_color = 128; sn_wide_kernels.h), float offsets, exact fp32 only.  Same
+// operand orders as SnMainImg with four 32-row tiles per 128-wide layer and 64 k-steps per 128-wide input.  Built by sn_weights.h
+// (build_wide_image).
+struct SnWideImg {
+    static constexpr int HIDDEN = 128;
+    static constexpr int W1 = 0;         // [rt=4][t4=4][lane=64][4]    32 -> 128
+    static constexpr int W2 = 4096;      // [rt=1][t4=16][64][4]        128 -> 32 rows (16 real + dup)
+    static constexpr int WC1 = 8192;     // [rt=4][t4=4][64][4]         (16 L2-rows + 16 SH) -> 128
+    static constexpr int WC2 = 12288;    // [rt=4][t4=16][64][4]        128 -> 128
+    static constexpr int B1 = 28672;     // [rt=4][h=2][16]
+    static constexpr int B2 = B1 + 128;  // [1][2][16]
+    static constexpr int BC1 = B2 + 32;  // [4][2][16]
+    static constexpr int BC2 = BC1 + 128;  // [4][2][16]
+    static constexpr int W3 = BC2 + 128;   // [n=3][h=2][64]: colour layer 3 on the VALU, [rt*16 + r] <-> hidden rt*32 + rho(r) + 4h
+    static constexpr int B3 = W3 + 3 * 128;  // [4]: the 3 biases
+    static constexpr int TOTAL = B3 + 4;     // 29 476 floats = 117 904 bytes; a multiple of 4
+    static constexpr int MAX_BINS = 1024 + 4;  // the uniform sampler's S + 1 euclidean bins behind the image (num_nerf_samples <= 1024)
+};
+static_assert(SnWideImg::TOTAL % 4 == 0, "the image is copied 16 bytes at a time");
+static_assert((SnWideImg::TOTAL + SnWideImg::MAX_BINS) * 4 <= 160 * 1024, "wide image + bins table must fit the CU's 160 KiB LDS");
+
 // byte offsets of the fp16x2 LDS image; weights [rt][s][hi|lo][lane][8 halves]
 struct SnMainImgH {
     static constexpr int W1 = 0;          // 2 rt x 2 s x 2 x 1 KiB

@@ -341,6 +341,83 @@ inline SnMainImages pack_main_images(const SnFieldDesc& d, const SnMainTensors& 
     return out;
 }
 
+// ---- wide main field (hidden_dim = hidden_dim_color = 128) ----------------------------------------------------------------------
+// The LDS image consumed by sn_wide_field_tile (sn_wide_kernels.h; offsets: sn_layout.h SnWideImg), exact fp32, no range conditioning
+// and no feature scale (a wide handle reads the uploaded table only).  Same operand orders as build_main_image:
+//   A operand of k-step t, lane (i = lane & 31, h = lane >> 5), row tile rt  <->  W[rt*32 + i][k(t, h)]
+//   k(t, h) of a 32-wide input (layer 1):        feature 2t + h
+//   k(t, h) of a 128-wide input (t = 0..63):     hidden unit (t/16)*32 + rho(t%16) + 4h   (the accumulator order of the layer before)
+//   colour layer 1: k-steps 0..7 <- layer-2 rows rho(t) + 4h (row 0 = h0 is no input), k-steps 8..15 <- SH component 2(t-8) + h
+// W1 [128,32], b1 [128]; W2 [16,128], b2 [16]; Wc1 [128,cin], bc1 [128]; Wc2 [128,128], bc2 [128]; Wc3 [3,128], bc3 [3]; app [A].
+inline std::vector<float> build_wide_image(const SnFieldDesc& d, const float* W1, const float* b1, const float* W2, const float* b2,
+                                           const float* Wc1, const float* bc1, const float* Wc2, const float* bc2, const float* Wc3,
+                                           const float* bc3, const float* app) {
+    constexpr int H = SnWideImg::HIDDEN, RT = H / 32, KH = H / 2;  // 4 row tiles, 64 k-steps over a 128-wide input
+    std::vector<float> img(SnWideImg::TOTAL, 0.0f);
+    const int geo = d.geo_feat_dim;            // 15
+    const int sh = d.sh_levels * d.sh_levels;  // 16
+    const int cin = sh + geo + d.appearance_embed_dim;
+    auto put = [&](int base, int KS, int rt, int t, int lane, float v) {
+        img[base + ((rt * (KS / 4) + t / 4) * 64 + lane) * 4 + (t % 4)] = v;
+    };
+    auto hid_of = [](int t, int h) { return (t / 16) * 32 + rho(t % 16) + 4 * h; };
+    auto l2src = [&](int row) { return row < 16 ? row : (row == 20 ? 0 : -1); };  // row 20 repeats h0 for the upper half-wave
+    for (int lane = 0; lane < 64; ++lane) {
+        const int i = lane & 31, h = lane >> 5;
+        for (int rt = 0; rt < RT; ++rt) {
+            const int row = rt * 32 + i;
+            for (int t = 0; t < 16; ++t) {
+                put(SnWideImg::W1, 16, rt, t, lane, W1[row * 32 + 2 * t + h]);
+                float v = 0.0f;
+                if (t < 8) {
+                    const int l2row = rho(t) + 4 * h;
+                    if (l2row >= 1 && l2row <= geo) v = Wc1[(size_t)row * cin + sh + (l2row - 1)];
+                } else {
+                    const int s = 2 * (t - 8) + h;
+                    if (s < sh) v = Wc1[(size_t)row * cin + s];
+                }
+                put(SnWideImg::WC1, 16, rt, t, lane, v);
+            }
+            for (int t = 0; t < KH; ++t) put(SnWideImg::WC2, KH, rt, t, lane, Wc2[row * H + hid_of(t, h)]);
+        }
+        for (int t = 0; t < KH; ++t) {
+            const int src = l2src(i);
+            put(SnWideImg::W2, KH, 0, t, lane, src >= 0 ? W2[src * H + hid_of(t, h)] : 0.0f);
+        }
+    }
+    // bias images [rt][h][r] -> bias[rt*32 + rho(r) + 4h]
+    auto bias_img = [&](int base, int nrt, auto&& f) {
+        for (int rt = 0; rt < nrt; ++rt)
+            for (int h = 0; h < 2; ++h)
+                for (int r = 0; r < 16; ++r) img[base + (rt * 2 + h) * 16 + r] = f(rt * 32 + rho(r) + 4 * h);
+    };
+    bias_img(SnWideImg::B1, RT, [&](int n) { return b1[n]; });
+    bias_img(SnWideImg::B2, 1, [&](int row) {
+        const int src = l2src(row);
+        return src >= 0 ? b2[src] : 0.0f;
+    });
+    bias_img(SnWideImg::BC1, RT, [&](int n) {  // the mean appearance embedding is a constant input: folded into the bias (A14)
+        float acc = bc1[n];
+        for (int a = 0; a < d.appearance_embed_dim; ++a) acc += Wc1[(size_t)n * cin + sh + geo + a] * app[a];
+        return acc;
+    });
+    bias_img(SnWideImg::BC2, RT, [&](int n) { return bc2[n]; });
+    for (int n = 0; n < 3; ++n)
+        for (int h = 0; h < 2; ++h)
+            for (int rt = 0; rt < RT; ++rt)
+                for (int r = 0; r < 16; ++r) img[SnWideImg::W3 + (n * 2 + h) * (H / 2) + rt * 16 + r] = Wc3[n * H + rt * 32 + rho(r) + 4 * h];
+    for (int n = 0; n < 3; ++n) img[SnWideImg::B3 + n] = bc3[n];
+    return img;
+}
+
+// true for the descriptor of a wide field: both MLPs of the main field are 128 wide (sn_create refuses mixed pairs)
+inline bool sn_is_wide(const SnFieldDesc& d) { return d.main_field.hidden_dim == SnWideImg::HIDDEN && d.hidden_dim_color == SnWideImg::HIDDEN; }
+
+inline std::vector<float> pack_wide_image(const SnFieldDesc& d, const SnMainTensors& p) {
+    return build_wide_image(d, p.W1->data(), p.b1->data(), p.W2->data(), p.b2->data(), p.Wc1->data(), p.bc1->data(), p.Wc2->data(),
+                            p.bc2->data(), p.Wc3->data(), p.bc3->data(), p.app->data());
+}
+
 // ---- normals ------------------------------------------------------------------------------------------------------------------
 // the pred-normal MLP w0 [64,12+geo], c0 [64]; w1 [64,64], c1 [64]; w2 [64,64], c2 [64] and its head wh [3,64], ch [3]: all or none
 struct SnPredNormalTensors {

@@ -406,6 +406,11 @@ class NerfactoModel(nn.Module):
                                       'tiny-cuda-nn checkpoints: it needs implementation="tcnn"; the torch-path parity target runs "fp16x2" / "fp32"')
         if cfg.proposal_initial_sampler not in INITIAL_SAMPLERS:
             raise NotImplementedError(f"proposal_initial_sampler={cfg.proposal_initial_sampler!r}: one of {sorted(INITIAL_SAMPLERS)} expected")
+        # a wide field (hidden_dim = hidden_dim_color = 128, nerfacto-big) has no normals kernel: the lazy "normals" / "pred_normals" surface
+        # the library's refusal when they are read, but "always" would make every render fail
+        if cfg.hidden_dim == 128 and cfg.predict_normals and cfg.compute_normals == "always":
+            raise NotImplementedError('compute_normals="always" with a wide field (hidden_dim=128): the normals kernel is not built for wide '
+                                      'fields; use compute_normals="lazy" (rgb / depth render, reading the normals raises) or "never"')
         self.field = NerfactoField(cfg, self.num_train_data)
         self.proposal_networks = nn.ModuleList()
         for i in range(cfg.num_proposal_iterations):
@@ -565,7 +570,11 @@ class NerfactoModel(nn.Module):
                     self._engine_rw.release_write()
         if not self._fallback_warned and self.effective_precision != self.config.precision:
             self._fallback_warned = True
-            warnings.warn(f"signerf_amd: precision={self.config.precision!r} cannot hold fp32 grade for these parameters; "
+            if self.config.hidden_dim == 128:   # a wide field: only the exact-fp32 MFMA arithmetic is built (DESIGN.md §4 "Wide fields")
+                why = "is not built for wide fields (hidden_dim=128)"
+            else:
+                why = "cannot hold fp32 grade for these parameters"
+            warnings.warn(f"signerf_amd: precision={self.config.precision!r} {why}; "
                           f"rendering with {self.effective_precision!r}", RuntimeWarning, stacklevel=3)
         return lib
 
