@@ -7,12 +7,14 @@ unchanged:
   * directory layout    datasetgenerator.py:146-182 (images/ masks/ conditions/ rendered/ originals/ *_<f>/ references/);
   * transforms.json     datasetgenerator.py:286-295 (header) and :447-466 (one frame per saved view);
   * ``load_previous_experiment_cameras``  signerf/utils/load_previous_experiment_cameras.py:12-54 (the reader of the same file).
-PNG encoding itself is PIL on the host, as in the reference.
+PNG encoding is on the host by default (``encode_png``: zlib on a pool of threads; "pil": the reference's literal call) or, with
+``png_encoder="hip"``, on the GPU (``encode_png_hip``: include/signerf_hip_png.h), after which the file buffer (the file and its length) crosses PCIe in one copy.
 """
 
 from __future__ import annotations
 
 import json
+import threading
 from pathlib import Path
 from typing import Any, Dict, List, Optional, Tuple, Union
 
@@ -111,6 +113,88 @@ def encode_png(u8, compress_level: int = 6) -> bytes:
             chunk(b"IDAT", zlib.compress(raw, int(compress_level))) + chunk(b"IEND", b""))
 
 
+class _PngHipSlot:
+    """The buffers of one encode in flight for a (shape, device): the device workspace, the device file with its byte count in the 8 bytes
+    before it (so ONE copy brings both) and the pinned host buffer that copy lands in.  The file's length is not known on the host when the
+    copy is enqueued, so the copy is of the whole capacity (``sn_png_max_file_bytes``: a little more than the raw pixels); the file is the
+    slice that is kept."""
+
+    def __init__(self, h: int, w: int, c: int, device: torch.device):
+        lib = _lib.load()
+        self.shape, self.device = (h, w, c), device
+        self.capacity = int(lib.sn_png_max_file_bytes(h, w, c))
+        ws = int(lib.sn_png_workspace_bytes(h, w, c))
+        if self.capacity == 0 or ws == 0:
+            raise ValueError(f"encode_png_hip: a [{h},{w},{c}] image is not encodable (1 or 3 channels, sides in 1..8192)")
+        self.workspace = torch.empty(ws, dtype=torch.uint8, device=device)
+        self.out = torch.empty(8 + self.capacity, dtype=torch.uint8, device=device)
+        self.host = torch.empty(8 + self.capacity, dtype=torch.uint8, pin_memory=True)
+        self.done = torch.cuda.Event()
+
+    def enqueue(self, u8: Tensor) -> None:
+        """Encode + the copy to the host, on the current stream; returns without waiting."""
+        lib = _lib.load()
+        h, w, c = self.shape
+        base = self.out.data_ptr()
+        _lib.check(lib.sn_png_encode(_lib.ptr(u8), h, w, c, self.workspace.data_ptr(), self.workspace.numel(), base + 8, self.capacity, base,
+                                     _lib.current_stream()), None, "sn_png_encode")
+        self.host.copy_(self.out, non_blocking=True)
+        self.done.record()
+        self.image = u8   # alive until the kernels have read it
+
+    def finish(self) -> bytes:
+        """The one synchronisation: waits for the copy, returns the file."""
+        self.done.synchronize()
+        self.image = None
+        n = int(self.host[:8].view(torch.int64).item())
+        assert 0 < n <= self.capacity, n
+        return self.host[8:8 + n].numpy().tobytes()
+
+
+_png_hip_slots: Dict[Tuple[int, int, int, int], List[_PngHipSlot]] = {}
+_png_hip_lock = threading.Lock()
+
+
+def _png_hip_acquire(u8: Tensor) -> _PngHipSlot:
+    h, w, c = (int(x) for x in u8.shape)
+    key = (h, w, c, u8.device.index if u8.device.index is not None else torch.cuda.current_device())
+    with _png_hip_lock:
+        free = _png_hip_slots.setdefault(key, [])
+        if free:
+            return free.pop()
+    return _PngHipSlot(h, w, c, u8.device)
+
+
+def _png_hip_release(slot: _PngHipSlot) -> None:
+    h, w, c = slot.shape
+    with _png_hip_lock:
+        free = _png_hip_slots.setdefault((h, w, c, slot.device.index if slot.device.index is not None else torch.cuda.current_device()), [])
+        if len(free) < 16:   # what is kept between calls; an encode in flight beyond it allocates
+            free.append(slot)
+
+
+def _png_hip_enqueue(u8: Tensor) -> _PngHipSlot:
+    if not (isinstance(u8, Tensor) and u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 3 and u8.shape[2] in (1, 3)):
+        raise ValueError("encode_png_hip: a uint8 [H,W,1] or [H,W,3] tensor on the GPU is expected")
+    u8 = u8.contiguous()
+    slot = _png_hip_acquire(u8)
+    with torch.cuda.device(u8.device):
+        slot.enqueue(u8)
+    return slot
+
+
+def encode_png_hip(u8: Tensor) -> bytes:
+    """The PNG file of a device uint8 [H,W,1] (greyscale) or [H,W,3] (RGB) tensor, encoded on the GPU (include/signerf_hip_png.h): the
+    pixels ``encode_png`` stores, in a file whose bytes depend on (pixels, shape) alone.  Workspace and pinned host buffer are cached per
+    (shape, device); one device-to-host copy (of the file buffer's whole capacity: the length arrives with it) and one synchronisation per
+    image.  There are no compression levels."""
+    slot = _png_hip_enqueue(u8)
+    try:
+        return slot.finish()
+    finally:
+        _png_hip_release(slot)
+
+
 class GeneratedDataset:
     """Directory + transforms.json writer with the reference's layout and keys."""
 
@@ -122,9 +206,12 @@ class GeneratedDataset:
         and the file writes run on that many host threads (zlib releases the GIL) while the caller goes on to the next view; the
         bytes of a file do not depend on it.  ``flush()`` waits for them.  png_compress_level: None = the reference's call
         (``Image.save(path)``, zlib level 6); 1 encodes ~2.3x faster into ~15 % larger files holding the same pixels.
-        png_encoder: "native" = ``encode_png`` above (same pixels, encodes in parallel on the pool); "pil" = the reference's literal call."""
-        if png_encoder not in ("native", "pil"):
-            raise ValueError(f"png_encoder={png_encoder!r}: 'native' or 'pil' expected")
+        png_encoder: "native" = ``encode_png`` above (same pixels, encodes in parallel on the pool); "pil" = the reference's literal call;
+        "hip" = ``encode_png_hip``: the GPU encodes, the pool (or the caller) only waits for the file and writes it.  It has no levels."""
+        if png_encoder not in ("native", "pil", "hip"):
+            raise ValueError(f"png_encoder={png_encoder!r}: 'native', 'pil' or 'hip' expected")
+        if png_encoder == "hip" and png_compress_level is not None:
+            raise ValueError("png_encoder='hip' has no compression levels: leave png_compress_level at None")
         self.png_encoder = png_encoder
         self.png_compress_level = png_compress_level
         self.dataset_path = Path(path) / dataset_name
@@ -132,6 +219,8 @@ class GeneratedDataset:
         self.write_images = write_images
         self.dirs: Dict[str, Path] = {}
         self._pool = None
+        self._png_streams: Dict[int, List] = {}   # device index -> side streams of the "hip" encoder
+        self._png_stream_next = 0
         self._pending: List = []
         # at most this many encodes queued or running: the host copies of a view's 8 PNGs must not pile up when encoding is slower than
         # the loop; a failed write surfaces at the next save instead of at the end
@@ -169,12 +258,36 @@ class GeneratedDataset:
 
     def save_image(self, tensor: Tensor, path: Path) -> None:
         """``tensor_to_image(tensor).save(path)``: the truncating uint8 cast on the GPU, one device-to-host copy of the bytes, PNG
-        encoding on the host (in the pool when there is one)."""
+        encoding on the host (in the pool when there is one); with png_encoder="hip" the encoding is on the GPU too and the copy
+        brings the file buffer."""
         if not self.write_images:
             return
         from PIL import Image
 
         assert len(tensor.shape) == 3 and tensor.shape[2] in (1, 3), "Tensor must be of shape (H, W, 1) or (H, W, 3)"
+        if self.png_encoder == "hip":
+            # Nothing waits here.  The cast runs on the current stream, so the caller's tensor is read in stream order.  The encode of one
+            # image is a few hundred workgroups of one wave, far from filling the GPU, so encode + copy of consecutive saves (a view's
+            # eight files) go round a few side streams, each behind the cast, and overlap one another and the next view's work.  The
+            # uint8 image is held until the file has arrived.
+            with torch.cuda.device(tensor.device):
+                u8 = tensor_to_uint8(tensor)
+                side = self._png_stream(tensor.device)
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    slot = _png_hip_enqueue(u8)
+
+            def write_file():
+                try:
+                    data = slot.finish()
+                finally:
+                    _png_hip_release(slot)
+                with open(path, "wb") as f:
+                    f.write(data)
+
+            # an encode in flight holds the uint8 image, a workspace, a device file and a pinned buffer, each of the image's size: few at a time
+            self._submit(write_file, limit=min(self._max_pending, 16))
+            return
         u8 = tensor_to_uint8(tensor).cpu().numpy()
 
         kw = {} if self.png_compress_level is None else {"compress_level": int(self.png_compress_level)}
@@ -189,10 +302,22 @@ class GeneratedDataset:
             else:
                 (Image.fromarray(u8.squeeze(), "L") if u8.shape[2] == 1 else Image.fromarray(u8)).save(path, **kw)
 
+        self._submit(write)
+
+    def _png_stream(self, device: torch.device) -> "torch.cuda.Stream":
+        """The next of the device's four side streams (made at the device's first save)."""
+        index = device.index if device.index is not None else torch.cuda.current_device()
+        streams = self._png_streams.get(index)
+        if streams is None:
+            streams = self._png_streams[index] = [torch.cuda.Stream(torch.device("cuda", index)) for _ in range(4)]
+        self._png_stream_next = (self._png_stream_next + 1) % len(streams)
+        return streams[self._png_stream_next]
+
+    def _submit(self, write, limit: Optional[int] = None) -> None:
         if self._pool is None:
             write()
         else:
-            while len(self._pending) >= self._max_pending:
+            while len(self._pending) >= (self._max_pending if limit is None else limit):
                 self._pending.pop(0).result()
             self._pending.append(self._pool.submit(write))
 

@@ -371,7 +371,7 @@ class DatasetGenerator:
                  png_compress_level: Optional[int] = None, finish_sync: bool = True, serial_stage_timeout_s: float = 24 * 3600.0,
                  precompute_budget_mb: Optional[int] = None, png_encoder: str = "native") -> None:
         self.config = config
-        self.png_encoder = png_encoder   # "native": dataset_io.encode_png (same pixels, parallel on the pool); "pil": the reference's Image.save
+        self.png_encoder = png_encoder   # "native": dataset_io.encode_png (same pixels, parallel on the pool); "pil": the reference's Image.save; "hip": encoded on the GPU
         self.finish_sync, self.serial_stage_timeout_s = finish_sync, serial_stage_timeout_s
         self.precompute_budget_mb, self.precompute_skipped = precompute_budget_mb, 0
         self.png_compress_level = png_compress_level   # None: PIL's default, the files the reference writes (dataset_io.GeneratedDataset)
