@@ -20,6 +20,7 @@ SN_MESH_RAYS_ABI_VERSION = 1   # include/signerf_hip_mesh_rays.h, checked the sa
 SN_MESH_MATERIAL_ABI_VERSION = 1   # include/signerf_hip_mesh_material.h, checked the same way
 SN_RAY_BATCH_ABI_VERSION = 1   # include/signerf_hip_ray_batch.h, checked the same way
 SN_PNG_ABI_VERSION = 1   # include/signerf_hip_png.h, checked the same way
+SN_LOSSES_ABI_VERSION = 1   # include/signerf_hip_losses.h, checked the same way
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # SIGNERF_HIP_LIB: load another build of the library (A/B experiments with tools/ab_lib.sh); the default is the in-tree build
@@ -309,6 +310,18 @@ PNG_SIGNATURES = {
     "sn_png_encode": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, _FP, C.c_size_t, _FP, C.c_void_p]),
 }
 
+# The companion header include/signerf_hip_losses.h (differentiable compositing and the sampler losses): every symbol it declares
+# (tests/test_losses_host.py checks them).
+LOSSES_SIGNATURES = {
+    "sn_losses_abi_version": (C.c_int, []),
+    "sn_loss_composite_forward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, _FP, _FP, _FP, C.c_void_p]),
+    "sn_loss_composite_backward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, _FP, _FP, _FP, _FP, _FP, C.c_void_p]),
+    "sn_loss_distortion_forward": (C.c_int, [_FP, _FP, C.c_int64, C.c_int32, _FP, C.c_void_p]),
+    "sn_loss_distortion_backward": (C.c_int, [_FP, _FP, _FP, C.c_int64, C.c_int32, _FP, C.c_void_p]),
+    "sn_loss_interlevel_forward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p]),
+    "sn_loss_interlevel_backward": (C.c_int, [_FP, _FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, _FP, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lock = threading.Lock()
 
@@ -334,7 +347,8 @@ def load() -> C.CDLL:
             raise SignerfHipError(f"cannot load {LIB_PATH}: {e}") from e
         for name, (res, args) in list(SIGNATURES.items()) + (list(MESH_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items())
                                          + list(MESH_RAYS_SIGNATURES.items()) + list(MESH_MATERIAL_SIGNATURES.items())
-                                         + list(RAY_BATCH_SIGNATURES.items()) + list(PNG_SIGNATURES.items())):
+                                         + list(RAY_BATCH_SIGNATURES.items()) + list(PNG_SIGNATURES.items())
+                                         + list(LOSSES_SIGNATURES.items())):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise SignerfHipError(f"{LIB_PATH} does not export {name}: it was built from another include/signerf_hip.h -- rebuild it "
@@ -368,6 +382,10 @@ def load() -> C.CDLL:
         if got != SN_PNG_ABI_VERSION:
             raise SignerfHipError(f"{LIB_PATH} reports SN_PNG_ABI_VERSION {got}, this binding was written for "
                                   f"{SN_PNG_ABI_VERSION}: rebuild the library")
+        got = lib.sn_losses_abi_version()
+        if got != SN_LOSSES_ABI_VERSION:
+            raise SignerfHipError(f"{LIB_PATH} reports SN_LOSSES_ABI_VERSION {got}, this binding was written for "
+                                  f"{SN_LOSSES_ABI_VERSION}: rebuild the library")
         _lib = lib
         return lib
 

@@ -105,11 +105,15 @@ class Frustums:
 
 @dataclass
 class RaySamples:
-    """nerfstudio's ``RaySamples`` as far as a Field reads it: ``frustums`` (+ ``camera_indices``, ``deltas``, unused in eval)."""
+    """nerfstudio's ``RaySamples`` as far as a Field reads it: ``frustums`` (+ ``camera_indices``, ``deltas``, unused in eval), and as far
+    as the sampler losses read it: ``spacing_starts`` / ``spacing_ends`` [..., S, 1], the samples' bins in normalised distance
+    (``losses.ray_samples_to_sdist``)."""
 
     frustums: Frustums
     camera_indices: Optional[Tensor] = None
     deltas: Optional[Tensor] = None
+    spacing_starts: Optional[Tensor] = None
+    spacing_ends: Optional[Tensor] = None
 
     @property
     def shape(self):

@@ -81,6 +81,14 @@ class NerfactoModelConfig(InstantiateConfig):
     num_train_data: int = 50
     """Rows of the appearance embedding table (the new dataset's size; signerf_pipeline.py:110-111 drops the
     trained table, so eval uses the mean of a freshly initialised one)."""
+    interlevel_loss_mult: float = 1.0
+    """Training: multiplier of the proposal (interlevel) loss in ``get_loss_dict`` [NS]."""
+    distortion_loss_mult: float = 0.002
+    """Training: multiplier of the distortion loss in ``get_loss_dict`` [NS]."""
+    orientation_loss_mult: float = 0.0001
+    """Training: multiplier of the orientation loss; it is formed only when the outputs hold ``rendered_orientation_loss`` [NS]."""
+    pred_normal_loss_mult: float = 0.001
+    """Training: multiplier of the predicted-normal loss; formed only when the outputs hold ``rendered_pred_normal_loss`` [NS]."""
     dense_levels: int = 0
     """Memory budget of the derived gather buffers the HIP library builds beside the uploaded tables (``SnFieldDesc.dense_levels``):
     0 = default (the 11 coarsest levels of the main grid get a de-hashed copy: 1.26 GB per model for nerfacto's grid, + 0.47 GB of x-paired

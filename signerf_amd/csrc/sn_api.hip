@@ -7,6 +7,7 @@
 #include "../../include/signerf_hip_mesh_material.h"
 #include "../../include/signerf_hip_ray_batch.h"
 #include "../../include/signerf_hip_png.h"
+#include "../../include/signerf_hip_losses.h"
 
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -36,6 +37,7 @@
 #include "sn_stage.h"
 #include "sn_ray_batch.h"
 #include "sn_png.h"
+#include "sn_losses.h"
 #include "sn_variant.h"
 #include "sn_weights.h"
 #include "sn_wide.h"
@@ -2113,6 +2115,132 @@ int sn_png_encode(const uint8_t* image, int32_t h, int32_t w, int32_t c, void* w
     else hipLaunchKernelGGL(sn_png_segment_deflate_kernel<3>, dim3(p.nseg), dim3(64), 0, st, p);
     hipLaunchKernelGGL(sn_png_finish_file_kernel, dim3(1), dim3(1024), 0, st, p);
     hipLaunchKernelGGL(sn_png_compact_bytes_kernel, dim3(p.nseg), dim3(256), 0, st, p);
+    return end_launches(who);
+}
+
+// ---- include/signerf_hip_losses.h: differentiable compositing and the sampler losses, one wave per ray ------------------------------------
+int sn_losses_abi_version(void) { return SN_LOSSES_ABI_VERSION; }
+static_assert(SN_LOSSES_MAX_SAMPLES == SN_LOSS_MAX_S, "the header's sample limit is the kernels'");
+
+// the checks every entry point shares; 1 = go on and launch, 0 = R == 0 (SN_OK, nothing to do), < 0 = refused (-status)
+static int losses_prologue(const std::string& who, int64_t R, int32_t S, int32_t P, bool pointers_ok, const char* pointers) {
+    if (R < 0) return -fail(nullptr, SN_ERR_INVALID, who + ": R must be >= 0");
+    if (S < 1 || S > SN_LOSS_MAX_S) return -fail(nullptr, SN_ERR_INVALID, who + ": S must lie in 1.." + std::to_string(SN_LOSS_MAX_S));
+    if (P < 1 || P > SN_LOSS_MAX_S) return -fail(nullptr, SN_ERR_INVALID, who + ": P must lie in 1.." + std::to_string(SN_LOSS_MAX_S));
+    if (R == 0) return 0;   // (an empty tensor's pointer may be NULL)
+    if (!pointers_ok) return -fail(nullptr, SN_ERR_INVALID, who + ": NULL argument (" + pointers + ")");
+    if (R > 0x7fffffffll) return -fail(nullptr, SN_ERR_INVALID, who + ": R exceeds the grid (2^31 - 1 rays)");
+    return 1;
+}
+
+int sn_loss_composite_forward(const float* deltas, const float* density, const float* colour, const float* background, int64_t R, int32_t S,
+                              float* weights, float* rgb, float* accumulation, SnStream stream) {
+    const std::string who = "sn_loss_composite_forward";
+    const bool ok = deltas && density && (weights || rgb || accumulation) && (colour || !rgb);
+    const int go = losses_prologue(who, R, S, 1, ok, "deltas, density; one output at least; colour with rgb");
+    if (go <= 0) return -go;
+    SnLossCompositeParams p;
+    memset(&p, 0, sizeof(p));
+    p.deltas = deltas;
+    p.density = density;
+    p.colour = colour;
+    p.background = background;
+    p.S = S;
+    p.weights = weights;
+    p.rgb = rgb;
+    p.accumulation = accumulation;
+    hipLaunchKernelGGL(sn_loss_composite_forward_kernel, dim3((unsigned)R), dim3(64), 0, (hipStream_t)stream, p);
+    return end_launches(who);
+}
+
+int sn_loss_composite_backward(const float* deltas, const float* density, const float* colour, const float* background, int64_t R, int32_t S,
+                               const float* grad_weights, const float* grad_rgb, const float* grad_acc, float* grad_density,
+                               float* grad_colour, SnStream stream) {
+    const std::string who = "sn_loss_composite_backward";
+    const bool ok = deltas && density && grad_density && (colour || (!grad_rgb && !grad_colour));
+    const int go = losses_prologue(who, R, S, 1, ok, "deltas, density, grad_density; colour with grad_rgb or grad_colour");
+    if (go <= 0) return -go;
+    SnLossCompositeParams p;
+    memset(&p, 0, sizeof(p));
+    p.deltas = deltas;
+    p.density = density;
+    p.colour = colour;
+    p.background = background;
+    p.S = S;
+    p.grad_weights = grad_weights;
+    p.grad_rgb = grad_rgb;
+    p.grad_acc = grad_acc;
+    p.grad_density = grad_density;
+    p.grad_colour = grad_colour;
+    hipLaunchKernelGGL(sn_loss_composite_backward_kernel, dim3((unsigned)R), dim3(64), 0, (hipStream_t)stream, p);
+    return end_launches(who);
+}
+
+int sn_loss_distortion_forward(const float* t, const float* w, int64_t R, int32_t S, float* loss, SnStream stream) {
+    const std::string who = "sn_loss_distortion_forward";
+    const int go = losses_prologue(who, R, S, 1, t && w && loss, "t, w, loss");
+    if (go <= 0) return -go;
+    SnLossDistortionParams p;
+    memset(&p, 0, sizeof(p));
+    p.t = t;
+    p.w = w;
+    p.S = S;
+    p.loss = loss;
+    hipLaunchKernelGGL(sn_loss_distortion_forward_kernel, dim3((unsigned)R), dim3(64), sn_loss_distortion_lds(S), (hipStream_t)stream, p);
+    return end_launches(who);
+}
+
+int sn_loss_distortion_backward(const float* t, const float* w, const float* grad_loss, int64_t R, int32_t S, float* grad_w, SnStream stream) {
+    const std::string who = "sn_loss_distortion_backward";
+    const int go = losses_prologue(who, R, S, 1, t && w && grad_loss && grad_w, "t, w, grad_loss, grad_w");
+    if (go <= 0) return -go;
+    SnLossDistortionParams p;
+    memset(&p, 0, sizeof(p));
+    p.t = t;
+    p.w = w;
+    p.grad_loss = grad_loss;
+    p.S = S;
+    p.grad_w = grad_w;
+    hipLaunchKernelGGL(sn_loss_distortion_backward_kernel, dim3((unsigned)R), dim3(64), sn_loss_distortion_lds(S), (hipStream_t)stream, p);
+    return end_launches(who);
+}
+
+int sn_loss_interlevel_forward(const float* t, const float* w, const float* t_env, const float* w_env, int64_t R, int32_t S, int32_t P,
+                               float* loss, float* w_outer, SnStream stream) {
+    const std::string who = "sn_loss_interlevel_forward";
+    const int go = losses_prologue(who, R, S, P, t && t_env && w_env && (loss || w_outer) && (w || !loss),
+                                   "t, t_env, w_env; loss or w_outer; w with loss");
+    if (go <= 0) return -go;
+    SnLossInterlevelParams p;
+    memset(&p, 0, sizeof(p));
+    p.t = t;
+    p.w = w;
+    p.t_env = t_env;
+    p.w_env = w_env;
+    p.S = S;
+    p.P = P;
+    p.loss = loss;
+    p.w_outer = w_outer;
+    hipLaunchKernelGGL(sn_loss_interlevel_forward_kernel, dim3((unsigned)R), dim3(64), sn_loss_interlevel_lds(S, P, false), (hipStream_t)stream, p);
+    return end_launches(who);
+}
+
+int sn_loss_interlevel_backward(const float* t, const float* w, const float* t_env, const float* w_env, const float* grad_loss, int64_t R,
+                                int32_t S, int32_t P, float* grad_w_env, SnStream stream) {
+    const std::string who = "sn_loss_interlevel_backward";
+    const int go = losses_prologue(who, R, S, P, t && w && t_env && w_env && grad_loss && grad_w_env, "t, w, t_env, w_env, grad_loss, grad_w_env");
+    if (go <= 0) return -go;
+    SnLossInterlevelParams p;
+    memset(&p, 0, sizeof(p));
+    p.t = t;
+    p.w = w;
+    p.t_env = t_env;
+    p.w_env = w_env;
+    p.grad_loss = grad_loss;
+    p.S = S;
+    p.P = P;
+    p.grad_w_env = grad_w_env;
+    hipLaunchKernelGGL(sn_loss_interlevel_backward_kernel, dim3((unsigned)R), dim3(64), sn_loss_interlevel_lds(S, P, true), (hipStream_t)stream, p);
     return end_launches(who);
 }
 

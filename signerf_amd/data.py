@@ -7,8 +7,8 @@ on the CPU, and turn the indices into rays with ``RayGenerator`` -> ``cameras.ge
 ``next_train`` takes the pair off a queue and moves it to the GPU.  Here cameras and the uint8 image stack live on the GPU: the indices are
 sampled there with torch ops, and one kernel writes rays and pixels.  Names and argument order are nerfstudio's.
 
-Not here: training-mode sampling, losses and gradients; per-ray distortion deltas and pose refinement; the multi-process
-``DataProcessor``; eval dataloaders (the reference's own are ``TODO: Implement``); eroded-mask and equirectangular-weighted samplers.
+Not here: training-mode sampling and the field's gradients (the losses and the compositing backward ARE built: signerf_amd/losses.py, the
+back half of a step); per-ray distortion deltas and pose refinement; the multi-process ``DataProcessor``; eval dataloaders (the reference's own are ``TODO: Implement``); eroded-mask and equirectangular-weighted samplers.
 """
 
 from __future__ import annotations

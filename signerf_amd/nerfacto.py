@@ -442,8 +442,50 @@ class NerfactoModel(nn.Module):
     def get_training_callbacks(self, training_callback_attributes=None) -> List:
         return []
 
+    def _gt_rgb(self, batch) -> Tensor:
+        image = batch["image"].to(self.device)
+        if image.shape[-1] != 3:
+            raise NotImplementedError(f"batch['image'] with {image.shape[-1]} channels: the losses take RGB images (alpha blending of the "
+                                      "ground truth is not built)")
+        return image
+
+    def get_metrics_dict(self, outputs, batch) -> dict:
+        """nerfstudio's NerfactoModel.get_metrics_dict [NS-RECALL]: ``psnr`` (data range 1), and while training ``distortion``, the mean
+        distortion loss of the main level (losses.distortion_loss, HIP) when the outputs hold ``weights_list``."""
+        from . import losses
+
+        mse = torch.mean((outputs["rgb"] - self._gt_rgb(batch)) ** 2)
+        metrics = {"psnr": -10.0 * torch.log10(mse)}
+        if self.training and "weights_list" in outputs:
+            metrics["distortion"] = losses.distortion_loss(outputs["weights_list"], outputs["ray_samples_list"])
+        return metrics
+
+    def _sampler_losses(self, outputs, metrics_dict) -> dict:
+        """The training-only terms nerfacto and SIGNeRF share: interlevel and distortion loss with the config's multipliers, and the two
+        normal losses when the outputs hold their per-ray terms (per-sample normals are not exposed, so a render of this package never does)."""
+        from . import losses
+
+        cfg = self.config
+        out = {"interlevel_loss": cfg.interlevel_loss_mult * losses.interlevel_loss(outputs["weights_list"], outputs["ray_samples_list"])}
+        if metrics_dict is not None and "distortion" in metrics_dict:
+            distortion = metrics_dict["distortion"]
+        else:
+            distortion = losses.distortion_loss(outputs["weights_list"], outputs["ray_samples_list"])
+        out["distortion_loss"] = cfg.distortion_loss_mult * distortion
+        if cfg.predict_normals:
+            if "rendered_orientation_loss" in outputs:
+                out["orientation_loss"] = cfg.orientation_loss_mult * torch.mean(outputs["rendered_orientation_loss"])
+            if "rendered_pred_normal_loss" in outputs:
+                out["pred_normal_loss"] = cfg.pred_normal_loss_mult * torch.mean(outputs["rendered_pred_normal_loss"])
+        return out
+
     def get_loss_dict(self, outputs, batch, metrics_dict=None) -> dict:
-        raise NotImplementedError("training losses are outside the render path (SURVEY.md §2 row 8)")
+        """nerfstudio's NerfactoModel.get_loss_dict [NS-RECALL]: ``rgb_loss`` (MSE) and, while training, ``interlevel_loss`` and
+        ``distortion_loss`` from ``outputs["weights_list"]`` / ``outputs["ray_samples_list"]`` (last entry: the main level)."""
+        loss_dict = {"rgb_loss": torch.mean((self._gt_rgb(batch) - outputs["rgb"]) ** 2)}
+        if self.training:
+            loss_dict.update(self._sampler_losses(outputs, metrics_dict))
+        return loss_dict
 
     # nerfstudio's MLPWithHashEncoding may register its torch-path pair as `model = nn.Sequential(encoder, mlp)` [NS-RECALL, M] -- a checkpoint then
     # holds `<...>.mlp_base.model.0.hash_table` / `<...>.mlp_base.model.1.layers.N.{weight,bias}` instead of (or beside) the `encoder.` / `mlp.` names
@@ -802,6 +844,33 @@ class NerfactoModel(nn.Module):
 
 
 class SIGNeRFModel(NerfactoModel):
-    """signerf.py:27-39: same render path; only training losses differ (out of scope here)."""
+    """signerf.py:27-82: the same render path; the training losses differ."""
 
     config: SIGNeRFModelConfig
+
+    def populate_modules(self):
+        super().populate_modules()
+        # The perceptual metric of the LPIPS term, ``lpips(pred, target)`` on [N, 3, patch, patch] images in [-1, 1] -> a scalar.  Its
+        # weights are not shipped: attach a module (``model.lpips = LearnedPerceptualImagePatchSimilarity()`` of torchmetrics, as
+        # signerf.py:39 does) or set ``use_lpips=False``.
+        self.lpips = None
+
+    def get_loss_dict(self, outputs, batch, metrics_dict=None) -> dict:
+        """signerf.py:41-82: L1 (``use_l1``) or MSE on the rgb, the LPIPS term on ``patch_size`` x ``patch_size`` patches normalised to
+        [-1, 1], and while training the sampler losses."""
+        cfg = self.config
+        image, output = self._gt_rgb(batch), outputs["rgb"]
+        loss_dict = {"rgb_loss": torch.mean(torch.abs(image - output)) if cfg.use_l1 else torch.mean((image - output) ** 2)}
+        if cfg.use_lpips:
+            lpips = getattr(self, "lpips", None)
+            if lpips is None:
+                raise NotImplementedError("use_lpips=True, but LPIPS weights are not shipped with this package: attach a module that maps "
+                                          "(pred, target) patches [N, 3, patch, patch] in [-1, 1] to a scalar as `model.lpips = ...` "
+                                          "(torchmetrics' LearnedPerceptualImagePatchSimilarity), or set use_lpips=False")
+            ps = cfg.patch_size
+            out_patches = (output.reshape(-1, ps, ps, 3).permute(0, 3, 1, 2) * 2 - 1).clamp(-1, 1)
+            gt_patches = (image.reshape(-1, ps, ps, 3).permute(0, 3, 1, 2) * 2 - 1).clamp(-1, 1)
+            loss_dict["lpips_loss"] = cfg.lpips_loss_mult * lpips(out_patches, gt_patches)
+        if self.training:
+            loss_dict.update(self._sampler_losses(outputs, metrics_dict))
+        return loss_dict
