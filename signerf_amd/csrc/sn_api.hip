@@ -43,6 +43,8 @@
 #include "sn_wide.h"
 #include "sn_wide_kernels.h"
 
+#include "sn_api_host.h"
+
 namespace {
 
 thread_local std::string g_create_error;
@@ -228,32 +230,12 @@ void mark_weights_written(SnHandle h, hipStream_t st) {
 
 thread_local std::string g_error_copy;  // sn_last_error hands out a per-thread copy: another thread may rewrite the handle's text
 
-int fail(SnHandle h, int code, const std::string& msg);
-
-// include/signerf_hip.h "ABI evolution": the caller's struct begins with the sizeof ITS header gives it.  Exactly that many bytes are
-// copied into the library's own (zeroed) struct: fields the caller does not know keep their zero defaults, nothing behind the caller's
-// struct is read.  min_size = the struct's size in the first versioned header (r06).
-template <typename T>
-int adopt_struct(SnHandle h, const T* in, size_t min_size, T& out, const char* what) {
-    memset((void*)&out, 0, sizeof(T));
-    uint32_t sz = 0;
-    memcpy(&sz, (const void*)in, sizeof(sz));
-    if (sz < min_size || sz > sizeof(T))
-        return fail(h, SN_ERR_INVALID, std::string(what) + ".struct_size = " + std::to_string(sz) + ": this library (SN_ABI_VERSION " + std::to_string(SN_ABI_VERSION) +
-                                           ") knows sizes " + std::to_string(min_size) + " .. " + std::to_string(sizeof(T)) +
-                                           (sz == 0 ? " -- struct_size was not set (set it to sizeof of the struct in your header)"
-                                                    : sz > sizeof(T) ? " -- the caller was built against a newer header than the library" : ""));
-    memcpy((void*)&out, (const void*)in, sz);
-    out.struct_size = (uint32_t)sizeof(T);
-    return SN_OK;
-}
 // Smallest struct_size accepted.  r06's header is the first versioned one, so no binding with a shorter struct exists yet; the lower bounds
 // are nevertheless set where the r04 / r05 appendices begin, so that the short-struct path -- the one a future appendix will rely on -- is a
 // path the tests execute today (tests/test_cabi.py, tests/test_gpu_abi.py: a caller that declares the shorter size and has garbage, a wild
 // pointer included, in the memory behind it).
 constexpr size_t kFieldDescMin = offsetof(SnFieldDesc, dense_levels);      // ... up to the r03 fields (disable_scene_contraction, aabb)
 constexpr size_t kRenderOptsMin = offsetof(SnRenderOpts, march_stats);     // ... up to the r03 fields (background, spacing_mode)
-constexpr size_t kMaskOptsMin = offsetof(SnMaskOpts, additional_depth_radius) + sizeof(float);
 constexpr size_t kDebugLayoutMin = offsetof(SnDebugLayout, table_bytes);   // ... up to feature_scale
 
 // SnRenderOpts.reuse_final_bins: what the final bins in a workspace belong to, kept on the HOST per workspace address (the library
@@ -345,12 +327,6 @@ int fail(SnHandle h, int code, const std::string& msg) {
     }
     return code;
 }
-
-#define SN_HIP(h, expr)                                                                              \
-    do {                                                                                             \
-        hipError_t _e = (expr);                                                                      \
-        if (_e != hipSuccess) return fail(h, SN_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 bool check_hashmlp(const SnHashMlpDesc& d, int levels, int hidden, int out, std::string& why) {
     if (d.num_levels != levels) why = "num_levels must be " + std::to_string(levels);
@@ -503,13 +479,13 @@ int build_half_grid(SnHandle h, const SnHashMlpDesc& d, const DevBuf& table, con
 #if SN_H16_PAIRS
     for (int l = nd; l < d.num_levels; ++l) {
         const uint64_t n = (uint64_t)n_t[l] * T;
-        hipLaunchKernelGGL(sn_build_pairs_h16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)table.ptr, (uint32_t*)rows.ptr, l,
+        hipLaunchKernelGGL(sn_build_pairs_h16_kernel, blocks_for(n), dim3(256), 0, st, (const float*)table.ptr, (uint32_t*)rows.ptr, l,
                            d.log2_hashmap_size, pinfo.base[l], n_t[l], scale);
     }
 #else
     if (rest > 0) {
         const uint64_t n = (uint64_t)rest << d.log2_hashmap_size;
-        hipLaunchKernelGGL(sn_build_rows_h16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)table.ptr, (uint32_t*)rows.ptr, nd, rest,
+        hipLaunchKernelGGL(sn_build_rows_h16_kernel, blocks_for(n), dim3(256), 0, st, (const float*)table.ptr, (uint32_t*)rows.ptr, nd, rest,
                            d.log2_hashmap_size, scale);
     }
 #endif
@@ -585,7 +561,7 @@ int build_pairs(SnHandle h, const SnHashMlpDesc& d, const DevBuf& table, DevBuf&
     for (int l = 0; l < d.num_levels; ++l) {
         const uint64_t n = (uint64_t)n_t[l] * T;
         if (n == 0) continue;
-        hipLaunchKernelGGL(sn_build_pairs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)table.ptr,
+        hipLaunchKernelGGL(sn_build_pairs_kernel, blocks_for(n), dim3(256), 0, st, (const float*)table.ptr,
                            (float*)pairs.ptr, l, d.log2_hashmap_size, info.base[l], n_t[l], scale);
     }
     SN_HIP(h, hipGetLastError());
@@ -1010,105 +986,6 @@ int sn_finalize_weights(SnHandle h, SnStream stream) {
     return SN_OK;
 }
 
-int sn_generate_rays_camera(const SnCameraDesc* cam, const float* coords, int64_t n_coords, float* origins, float* directions,
-                            float* pixel_area, float* directions_norm, const float* aabb, float* nears, float* fars, SnStream stream) {
-    if (!cam || cam->height <= 0 || cam->width <= 0 || (coords && n_coords < 0))
-        return fail(nullptr, SN_ERR_INVALID, "sn_generate_rays_camera: bad argument");
-    if (cam->camera_type != SN_CAMERA_PERSPECTIVE && cam->camera_type != SN_CAMERA_FISHEYE && cam->camera_type != SN_CAMERA_EQUIRECTANGULAR)
-        return fail(nullptr, SN_ERR_INVALID, "sn_generate_rays_camera: camera_type " + std::to_string(cam->camera_type) +
-                                                 " is not supported (1 = PERSPECTIVE, 2 = FISHEYE, 3 = EQUIRECTANGULAR)");
-    SnRayGenParams p;
-    memcpy(p.c2w, cam->c2w, sizeof(p.c2w));
-    p.fx = cam->fx;
-    p.fy = cam->fy;
-    p.cx = cam->cx;
-    p.cy = cam->cy;
-    p.height = cam->height;
-    p.width = cam->width;
-    p.camera_type = cam->camera_type;
-    p.has_distortion = cam->has_distortion != 0 && cam->camera_type != SN_CAMERA_EQUIRECTANGULAR;  // (nerfstudio never un-distorts equirectangular images)
-    memcpy(p.dist, cam->distortion, sizeof(p.dist));
-    p.coords = coords;
-    p.n = coords ? n_coords : (int64_t)cam->height * cam->width;
-    p.origins = origins;
-    p.directions = directions;
-    p.pixel_area = pixel_area;
-    p.directions_norm = directions_norm;
-    p.has_aabb = aabb != nullptr;
-    if (aabb) memcpy(p.aabb, aabb, sizeof(p.aabb));
-    else memset(p.aabb, 0, sizeof(p.aabb));
-    p.nears = nears;
-    p.fars = fars;
-    if (p.n == 0) return SN_OK;
-    const dim3 grid((unsigned)((p.n + 255) / 256)), block(256);
-    const bool fish = cam->camera_type == SN_CAMERA_FISHEYE;
-    if (cam->camera_type == SN_CAMERA_EQUIRECTANGULAR) hipLaunchKernelGGL((sn_generate_rays_kernel<3, false>), grid, block, 0, (hipStream_t)stream, p);
-    else if (fish && p.has_distortion) hipLaunchKernelGGL((sn_generate_rays_kernel<2, true>), grid, block, 0, (hipStream_t)stream, p);
-    else if (fish) hipLaunchKernelGGL((sn_generate_rays_kernel<2, false>), grid, block, 0, (hipStream_t)stream, p);
-    else if (p.has_distortion) hipLaunchKernelGGL((sn_generate_rays_kernel<1, true>), grid, block, 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((sn_generate_rays_kernel<1, false>), grid, block, 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_generate_rays launch: ") + hipGetErrorString(e));
-    return SN_OK;
-}
-
-int sn_generate_rays(const float* c2w, float fx, float fy, float cx, float cy, int32_t height, int32_t width, float* origins,
-                     float* directions, float* pixel_area, float* directions_norm, const float* aabb, float* nears, float* fars,
-                     SnStream stream) {
-    if (!c2w || height <= 0 || width <= 0) return fail(nullptr, SN_ERR_INVALID, "sn_generate_rays: bad argument");
-    SnCameraDesc cam;
-    memset(&cam, 0, sizeof(cam));
-    memcpy(cam.c2w, c2w, sizeof(cam.c2w));
-    cam.fx = fx;
-    cam.fy = fy;
-    cam.cx = cx;
-    cam.cy = cy;
-    cam.height = height;
-    cam.width = width;
-    cam.camera_type = SN_CAMERA_PERSPECTIVE;
-    return sn_generate_rays_camera(&cam, nullptr, 0, origins, directions, pixel_area, directions_norm, aabb, nears, fars, stream);
-}
-
-int sn_intersect_with_aabb(const float* origins, const float* directions, int64_t n_rays, const float* aabb, float* nears,
-                           float* fars, SnStream stream) {
-    if (!origins || !directions || !aabb || !nears || !fars || n_rays < 0)
-        return fail(nullptr, SN_ERR_INVALID, "sn_intersect_with_aabb: bad argument");
-    if (n_rays == 0) return SN_OK;
-    SnAabb box;
-    memcpy(box.v, aabb, sizeof(box.v));
-    hipLaunchKernelGGL(sn_intersect_with_aabb_kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       origins, directions, n_rays, box, nears, fars);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_intersect_with_aabb launch: ") + hipGetErrorString(e));
-    return SN_OK;
-}
-
-int sn_intersect_obb(const float* origins, const float* directions, int64_t n_rays, const float* world2box, const float* size,
-                     float* nears, float* fars, SnStream stream) {
-    if (!origins || !directions || !world2box || !size || !nears || !fars || n_rays < 0)
-        return fail(nullptr, SN_ERR_INVALID, "sn_intersect_obb: bad argument");
-    if (n_rays == 0) return SN_OK;
-    SnObb box;
-    memcpy(box.w2b, world2box, sizeof(box.w2b));
-    for (int c = 0; c < 3; ++c) box.half[c] = size[c] / 2.0f;
-    hipLaunchKernelGGL(sn_intersect_obb_kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, (hipStream_t)stream, origins,
-                       directions, n_rays, box, nears, fars);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_intersect_obb launch: ") + hipGetErrorString(e));
-    return SN_OK;
-}
-
-int sn_debug_sample_positions(const float* origins, const float* directions, const float* starts, const float* ends, int64_t n,
-                              float* q_strict, float* q_exact, float* q_fast, SnStream stream) {
-    if (!origins || !directions || !starts || !ends || n < 0) return fail(nullptr, SN_ERR_INVALID, "sn_debug_sample_positions: bad argument");
-    if (n == 0) return SN_OK;
-    hipLaunchKernelGGL(sn_debug_sample_positions_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, origins,
-                       directions, starts, ends, n, q_strict, q_exact, q_fast);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_debug_sample_positions launch: ") + hipGetErrorString(e));
-    return SN_OK;
-}
-
 size_t sn_workspace_bytes(SnHandle h, int32_t height, int32_t width, const SnRenderOpts* opts_in) {
     if (!h || !opts_in || height <= 0 || width <= 0) return 0;
     SnRenderOpts own;
@@ -1271,7 +1148,7 @@ static int render_rays_impl(SnHandle h, const float* origins, const float* direc
         SN_HIP(h, hipGetLastError());
     }
     if (expected_depth) {
-        hipLaunchKernelGGL(sn_clip_expected_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_exp_raw, d_minmax, n,
+        hipLaunchKernelGGL(sn_clip_expected_kernel, blocks_for(n), dim3(256), 0, st, d_exp_raw, d_minmax, n,
                            opts->chunk_rays, wp.n_chunks, expected_depth);
         SN_HIP(h, hipGetLastError());
     }
@@ -1351,39 +1228,6 @@ int sn_debug_read(SnHandle h, int32_t which, int32_t what, void* dst, size_t byt
     if (!src || !src->ptr) return fail(h, SN_ERR_INVALID, "sn_debug_read: no such buffer");
     if (bytes != src->bytes) return fail(h, SN_ERR_INVALID, "sn_debug_read: expected " + std::to_string(src->bytes) + " bytes");
     SN_HIP(h, hipMemcpyAsync(dst, src->ptr, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return SN_OK;
-}
-
-// one wave per workgroup: shader-clock cycles (s_memtime) elapsed while the constant-rate wall clock (s_memrealtime) advances by `ticks`.
-// EIGHT workgroups, one per XCD (the dispatcher places block b on XCD b % 8): the XCDs of one part do not run at one clock under load
-// (measured r04, profiles/r04_power_data_activity.txt: 1.84 .. 1.99 GHz side by side, persistently), so a single wave reports whichever die it
-// lands on; the sums over the eight give the mean.
-__global__ void sn_clock_probe_kernel(unsigned long long* out, unsigned long long ticks) {
-    const unsigned long long r0 = wall_clock64();
-    const unsigned long long c0 = __builtin_readcyclecounter();
-    while (wall_clock64() - r0 < ticks) __builtin_amdgcn_s_sleep(32);
-    const unsigned long long c1 = __builtin_readcyclecounter();
-    const unsigned long long r1 = wall_clock64();
-    if (threadIdx.x == 0) {
-        atomicAdd(&out[0], c1 - c0);
-        atomicAdd(&out[1], r1 - r0);
-    }
-}
-
-int sn_clock_probe(uint64_t* out, double seconds, SnStream stream) {
-    if (!out || !(seconds > 0.0) || seconds > 1.0) return fail(nullptr, SN_ERR_INVALID, "sn_clock_probe: bad argument (0 < seconds <= 1)");
-    int dev = 0, khz = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0)
-        return fail(nullptr, SN_ERR_HIP, "sn_clock_probe: cannot read the wall-clock rate of the device");
-    const unsigned long long rate = (unsigned long long)khz * 1000ull;
-    const unsigned long long ticks = (unsigned long long)(seconds * (double)rate);
-    hipError_t e = hipMemsetAsync(out, 0, 16, (hipStream_t)stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(sn_clock_probe_kernel, dim3(8), dim3(64), 0, (hipStream_t)stream, (unsigned long long*)out, ticks);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out + 2, &rate, 8, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_clock_probe: ") + hipGetErrorString(e));
     return SN_OK;
 }
 
@@ -1480,7 +1324,7 @@ int sn_hash_encode(SnHandle h, int32_t which, const float* q, int64_t n, float* 
     else memset(&p.pinfo, 0, sizeof(p.pinfo));
     p.pairs_bytes = which >= 0 ? (uint32_t)h->pairs_prop[which].bytes : 0u;
     p.inv_pair_scale = which >= 0 ? 1.0f / h->feat_scale_prop[which] : 1.0f;
-    hipLaunchKernelGGL(sn_hash_encode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(sn_hash_encode_kernel, blocks_for(n), dim3(256), 0, (hipStream_t)stream, p);
     SN_HIP(h, hipGetLastError());
     return SN_OK;
 }
@@ -1527,11 +1371,11 @@ int sn_field_forward_geo(SnHandle h, int32_t which, const float* positions, cons
             const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, std::max(h->n_cus, 1));
             hipLaunchKernelGGL(sn_wide_field_stage_kernel, dim3(grid), dim3(256), (size_t)SnWideImg::TOTAL * 4, st, p);
         } else if (precision == 0)
-            hipLaunchKernelGGL(sn_main_field_stage_kernel<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), (size_t)SnMainImg::TOTAL * 4, st, p);
+            hipLaunchKernelGGL(sn_main_field_stage_kernel<0>, blocks_for(n), dim3(256), (size_t)SnMainImg::TOTAL * 4, st, p);
         else if (precision == 2)
-            hipLaunchKernelGGL(sn_main_field_stage_kernel<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), (size_t)SnMainImgF16::TOTAL_BYTES, st, p);
+            hipLaunchKernelGGL(sn_main_field_stage_kernel<2>, blocks_for(n), dim3(256), (size_t)SnMainImgF16::TOTAL_BYTES, st, p);
         else
-            hipLaunchKernelGGL(sn_main_field_stage_kernel<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), (size_t)SnMainImg::TOTAL * 4, st, p);
+            hipLaunchKernelGGL(sn_main_field_stage_kernel<1>, blocks_for(n), dim3(256), (size_t)SnMainImg::TOTAL * 4, st, p);
     } else {
         SnPropStageParams p;
         p.pm = h->pos_map;
@@ -1550,731 +1394,18 @@ int sn_field_forward_geo(SnHandle h, int32_t which, const float* positions, cons
         p.grid_mode = h->desc.proposals[which].grid_mode;
         p.grid = grid_levels(h->desc.proposals[which]);
         p.feat_scale = h->feat_scale_prop[which];
-        hipLaunchKernelGGL(sn_prop_field_stage_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
+        hipLaunchKernelGGL(sn_prop_field_stage_kernel, blocks_for(n), dim3(256), 0, st, p);
     }
     SN_HIP(h, hipGetLastError());
     return SN_OK;
 }
 
-int sn_composite(const float* euclid_bins, const float* density, const float* rgb_samples, int64_t n_rays, int32_t n_samples,
-                 float* weights, float* rgb, float* depth, int32_t* median_index, float* accumulation, float* expected_depth,
-                 SnStream stream) {
-    if (!euclid_bins || !density || !rgb_samples || n_rays < 0 || n_samples < 1)
-        return fail(nullptr, SN_ERR_INVALID, "sn_composite: bad argument");
-    if (n_rays == 0) return SN_OK;
-    hipStream_t st = (hipStream_t)stream;
-    SnCompositeStageParams p;
-    p.bins = euclid_bins;
-    p.density = density;
-    p.rgb_s = rgb_samples;
-    p.n_rays = n_rays;
-    p.n_samples = n_samples;
-    p.weights = weights;
-    p.rgb = rgb;
-    p.depth = depth;
-    p.median_index = median_index;
-    p.acc = accumulation;
-    p.exp_raw = nullptr;
-    p.minmax = nullptr;
-    uint32_t* mm = nullptr;
-    if (expected_depth) {
-        // expected_depth doubles as the raw buffer; min/max live in a small stream-ordered allocation
-        if (hipMallocAsync((void**)&mm, 8, st) != hipSuccess) return fail(nullptr, SN_ERR_HIP, "sn_composite: hipMallocAsync failed");
-        if (hipMemsetAsync(mm, 0xff, 4, st) != hipSuccess || hipMemsetAsync(mm + 1, 0x00, 4, st) != hipSuccess)
-            return fail(nullptr, SN_ERR_HIP, "sn_composite: memset failed");
-        p.exp_raw = expected_depth;
-        p.minmax = mm;
-    }
-    hipLaunchKernelGGL(sn_composite_kernel, dim3((unsigned)((n_rays + 127) / 128)), dim3(128), 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && expected_depth) {
-        hipLaunchKernelGGL(sn_clip_expected_kernel, dim3((unsigned)((n_rays + 255) / 256)), dim3(256), 0, st, expected_depth, mm, n_rays,
-                           0x7fffffff, 1, expected_depth);
-        e = hipGetLastError();
-        (void)hipFreeAsync(mm, st);
-    }
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_composite launch: ") + hipGetErrorString(e));
-    return SN_OK;
-}
-
-int sn_pdf_sample(const float* spacing_bins, const float* weights, int64_t n_rays, int32_t n_in, int32_t n_out, const float* u,
-                  float histogram_padding, float* new_bins, int32_t* inds, SnStream stream) {
-    if (!spacing_bins || !weights || !u || !new_bins || n_rays < 0 || n_in < 1 || n_in > SN_PROP_MAX_SAMPLES || n_out < 1 ||
-        n_out > SN_PROP_MAX_SAMPLES)
-        return fail(nullptr, SN_ERR_INVALID, "sn_pdf_sample: bad argument");
-    if (n_rays == 0) return SN_OK;
-    SnPdfStageParams p;
-    p.sbins = spacing_bins;
-    p.weights = weights;
-    p.n_rays = n_rays;
-    p.n_in = n_in;
-    p.n_out = n_out;
-    p.u = u;
-    p.hist_pad = histogram_padding;
-    p.new_bins = new_bins;
-    p.inds = inds;
-    hipLaunchKernelGGL(sn_pdf_stage_kernel, dim3((unsigned)((n_rays + 63) / 64)), dim3(64), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_pdf_sample launch: ") + hipGetErrorString(e));
-    return SN_OK;
-}
-
-
-size_t sn_mask_workspace_bytes(int32_t height, int32_t width) {
-    if (height <= 0 || width <= 0) return 0;
-    const size_t n = (size_t)height * width;
-    return align256(n) + align256((size_t)height * (width + 1) * 4) + 256;
-}
-
-// The part of SnMaskParams both masking modes share: options (opts already adopted and validated), the elliptical element, the
-// workspace carve-up (sn_mask_workspace_bytes) and the outputs.
-static void fill_mask_params(const SnMaskOpts* opts, const float* depth, int32_t height, int32_t width, void* workspace, uint8_t* mask,
-                             float* condition, SnMaskParams& p) {
-    const size_t n = (size_t)height * width;
-    memset(&p, 0, sizeof(p));
-    p.depth = depth;
-    p.height = height;
-    p.width = width;
-    p.inverse_mask = opts->inverse_mask;
-    p.dilate = opts->dilate_w > 0;
-    if (p.dilate) {
-        // cv2.getStructuringElement(cv2.MORPH_ELLIPSE, (w, h)): row i covers [c - dx, c + dx + 1) with
-        // dx = round(c * sqrt((r*r - dy*dy) / (r*r))), r = h/2, c = w/2, dy = i - r (rows with |dy| > r are empty)
-        const int kw = opts->dilate_w, kh = opts->dilate_h;
-        const int r = kh / 2, c = kw / 2;
-        const double inv_r2 = r ? 1.0 / ((double)r * r) : 0.0;
-        p.el.kw = kw;
-        p.el.kh = kh;
-        p.el.ax = kw / 2;
-        p.el.ay = kh / 2;
-        for (int i = 0; i < kh; ++i) {
-            int j1 = 0, j2 = 0;
-            if (kw == 1 && kh == 1) j2 = 1;  // a 1x1 element is a rectangle
-            else {
-                const int dy = i - r;
-                if (std::abs(dy) <= r) {
-                    const int dx = (int)std::nearbyint(c * std::sqrt((r * r - dy * dy) * inv_r2));
-                    j1 = std::max(c - dx, 0);
-                    j2 = std::min(c + dx + 1, kw);
-                }
-            }
-            p.el.j1[i] = (short)j1;
-            p.el.j2[i] = (short)j2;
-        }
-    }
-    p.has_manual_depth = opts->has_manual_depth;
-    p.manual_min = (float)opts->manual_min;
-    p.manual_range = (float)(opts->manual_max - opts->manual_min);
-    p.depth_radius = opts->additional_depth_radius;
-    char* ws = (char*)workspace;
-    p.vis = (uint8_t*)ws;
-    p.prefix = (int32_t*)(ws + align256(n));
-    p.stats = (uint32_t*)(ws + align256(n) + align256((size_t)height * (width + 1) * 4));
-    p.mask = mask;
-    p.condition = condition;
-}
-
-// What the three mask entry points share, for the entry point `who`: adopt and validate SnMaskOpts, check the workspace and clear
-// its stamp, fill p (fill_mask_params) and reset the three statistics words on the stream.
-static int begin_mask_step(const std::string& who, const SnMaskOpts* opts, const float* depth, int32_t height, int32_t width, uint8_t* mask,
-                           float* condition, void* workspace, size_t workspace_bytes, hipStream_t st, SnMaskParams& p) {
-    SnMaskOpts o;
-    if (int rc = adopt_struct(nullptr, opts, kMaskOptsMin, o, (who + ": SnMaskOpts").c_str())) return rc;
-    if (o.dilate_w < 0 || o.dilate_h < 0 || o.dilate_w > SN_MASK_MAX_K || o.dilate_h > SN_MASK_MAX_K || ((o.dilate_w == 0) != (o.dilate_h == 0)))
-        return fail(nullptr, SN_ERR_INVALID, who + ": dilation size must be 0 or within [1," + std::to_string(SN_MASK_MAX_K) + "] in both dimensions");
-    if (!workspace || workspace_bytes < sn_mask_workspace_bytes(height, width)) return fail(nullptr, SN_ERR_WORKSPACE, who + ": workspace too small");
-    clear_stamp(workspace);  // (a caller may hand the mask step the memory a render used: its bins are gone then)
-    fill_mask_params(&o, depth, height, width, workspace, mask, condition, p);
-    hipError_t e = hipMemsetAsync(p.stats, 0, 4, st);                    // count
-    if (e == hipSuccess) e = hipMemsetAsync(p.stats + 1, 0xff, 4, st);  // ordered min
-    if (e == hipSuccess) e = hipMemsetAsync(p.stats + 2, 0, 4, st);     // ordered max
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, who + " memset: " + hipGetErrorString(e));
-    return SN_OK;
-}
-
-static int end_launches(const std::string& who) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, who + " launch: " + hipGetErrorString(e));
-    return SN_OK;
-}
-
-static dim3 mask_visible_grid(size_t n) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, SN_MASK_VIS_BLOCKS)); }
-static dim3 per_pixel_grid(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
-
-int sn_aabb_mask_condition(const float* origins, const float* directions, const float* depth, int32_t height, int32_t width,
-                           const float* aabb, const SnMaskOpts* opts, uint8_t* mask, float* condition, void* workspace,
-                           size_t workspace_bytes, SnStream stream) {
-    const std::string who = "sn_aabb_mask_condition";
-    if (!origins || !directions || !depth || !aabb || !opts || !mask || height <= 0 || width <= 0)
-        return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t n = (size_t)height * width;
-    SnMaskParams p;
-    if (int rc = begin_mask_step(who, opts, depth, height, width, mask, condition, workspace, workspace_bytes, st, p)) return rc;
-    p.origins = origins;
-    p.directions = directions;
-    memcpy(p.aabb, aabb, sizeof(p.aabb));
-    hipLaunchKernelGGL(sn_mask_visible_kernel, mask_visible_grid(n), dim3(256), 0, st, p);
-    if (p.dilate) hipLaunchKernelGGL(sn_mask_prefix_kernel, dim3((unsigned)height), dim3(64), 0, st, p);
-    hipLaunchKernelGGL(sn_mask_condition_kernel, per_pixel_grid(n), dim3(256), 0, st, p);
-    return end_launches(who);
-}
-
-
-// ---- include/signerf_hip_mesh.h: the "shape" masking mode ---------------------------------------------------------------------------
-int sn_mesh_abi_version(void) { return SN_MESH_ABI_VERSION; }
-
-constexpr size_t kMeshRasterOptsMin = sizeof(SnMeshRasterOpts);  // the first layout
-#define SN_MESH_MAX_DIM 16384               // the tile records pack pixel coordinates into 16 bits
-#define SN_MESH_MAX_TRIS ((int64_t)1 << 30)  // int32 triangle indexing in the kernels, with room for a batch past the end
-
-size_t sn_mesh_workspace_bytes(int64_t n_triangles, int32_t height, int32_t width) {
-    if (n_triangles < 0 || n_triangles > SN_MESH_MAX_TRIS || height <= 0 || width <= 0 || height > SN_MESH_MAX_DIM || width > SN_MESH_MAX_DIM)
-        return 0;
-    const size_t f = (size_t)n_triangles;
-    return align256(f * sizeof(SnMeshTri)) + align256(f * sizeof(uint2)) + 256;
-}
-
-// What the two rasters share, for the entry point `who`: the checks of the mesh, the camera, SnMeshRasterOpts and the workspace (whose
-// stamp is cleared), and the SnMeshRasterParams.  `outputs_ok`: the entry point's own required pointers are there.
-static int begin_raster(const std::string& who, bool outputs_ok, const float* vertices, int64_t n_vertices, const int32_t* triangles,
-                        int64_t n_triangles, const float* model_view, float fx, float fy, float cx, float cy, int32_t height, int32_t width,
-                        const SnMeshRasterOpts* opts, float* depth, void* workspace, size_t workspace_bytes, SnMeshRasterParams& p) {
-    if (!outputs_ok || !model_view || !opts || n_vertices < 0 || n_triangles < 0 || n_triangles > SN_MESH_MAX_TRIS || height <= 0 || width <= 0 ||
-        height > SN_MESH_MAX_DIM || width > SN_MESH_MAX_DIM || (n_triangles > 0 && (!vertices || !triangles || n_vertices == 0)))
-        return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
-    SnMeshRasterOpts o;
-    if (int rc = adopt_struct(nullptr, opts, kMeshRasterOptsMin, o, (who + ": SnMeshRasterOpts").c_str())) return rc;
-    if (!(o.znear > 0.0f) || !(o.zfar > o.znear) || !std::isfinite(o.zfar)) return fail(nullptr, SN_ERR_INVALID, who + ": need 0 < znear < zfar < inf");
-    if (!(fx != 0.0f) || !(fy != 0.0f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
-        return fail(nullptr, SN_ERR_INVALID, who + ": intrinsics must be finite with fx, fy != 0");
-    if (!workspace || workspace_bytes < sn_mesh_workspace_bytes(n_triangles, height, width))
-        return fail(nullptr, SN_ERR_WORKSPACE, who + ": workspace too small");
-    clear_stamp(workspace);
-    memset(&p, 0, sizeof(p));
-    p.vertices = vertices;
-    p.tris = triangles;
-    p.n_vertices = n_vertices;
-    p.n_tris = (int32_t)n_triangles;
-    memcpy(p.mv, model_view, sizeof(p.mv));
-    p.fx = fx;
-    p.fy = fy;
-    p.cx = cx;
-    p.cy = cy;
-    p.height = height;
-    p.width = width;
-    p.znear = o.znear;
-    p.zfar = o.zfar;
-    p.cull = o.cull_back_faces != 0;
-    char* ws = (char*)workspace;
-    p.rec = (SnMeshTri*)ws;
-    p.bbox = (uint2*)(ws + align256((size_t)n_triangles * sizeof(SnMeshTri)));
-    p.depth = depth;
-    return SN_OK;
-}
-
-// M-a over the triangles; returns the grid of the tile kernel (M-b or M-e) that follows it
-static dim3 launch_mesh_setup(const SnMeshRasterParams& p, hipStream_t st) {
-    if (p.n_tris > 0) hipLaunchKernelGGL(sn_mesh_setup_kernel, dim3((unsigned)((p.n_tris + 255) / 256)), dim3(256), 0, st, p);
-    return dim3((unsigned)((p.width + SN_MESH_TILE - 1) / SN_MESH_TILE), (unsigned)((p.height + SN_MESH_TILE - 1) / SN_MESH_TILE));
-}
-
-int sn_mesh_raster_depth(const float* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, const float* model_view,
-                         float fx, float fy, float cx, float cy, int32_t height, int32_t width, const SnMeshRasterOpts* opts, float* depth,
-                         void* workspace, size_t workspace_bytes, SnStream stream) {
-    const std::string who = "sn_mesh_raster_depth";
-    SnMeshRasterParams p;
-    if (int rc = begin_raster(who, depth != nullptr, vertices, n_vertices, triangles, n_triangles, model_view, fx, fy, cx, cy, height, width, opts,
-                              depth, workspace, workspace_bytes, p))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sn_mesh_tile_kernel, launch_mesh_setup(p, st), dim3(SN_MESH_BATCH), 0, st, p);
-    return end_launches(who);
-}
-
-int sn_shape_mask_condition(const float* mesh_depth, const float* nerf_depth, int32_t height, int32_t width, const SnMaskOpts* opts,
-                            uint8_t* mask, float* condition, void* workspace, size_t workspace_bytes, SnStream stream) {
-    const std::string who = "sn_shape_mask_condition";
-    if (!mesh_depth || !nerf_depth || !opts || !mask || height <= 0 || width <= 0)
-        return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t n = (size_t)height * width;
-    SnShapeMaskParams sp;
-    if (int rc = begin_mask_step(who, opts, nerf_depth, height, width, mask, condition, workspace, workspace_bytes, st, sp.m)) return rc;
-    sp.mesh_depth = mesh_depth;
-    hipLaunchKernelGGL(sn_shape_visible_kernel, mask_visible_grid(n), dim3(256), 0, st, sp);
-    if (sp.m.dilate) hipLaunchKernelGGL(sn_mask_prefix_kernel, dim3((unsigned)height), dim3(64), 0, st, sp.m);
-    hipLaunchKernelGGL(sn_shape_condition_kernel, per_pixel_grid(n), dim3(256), 0, st, sp);
-    return end_launches(who);
-}
-
-
-// ---- include/signerf_hip_mesh_color.h: the mesh's colour image, aabb mode with combine_shape_with_depth ------------------------------
-int sn_mesh_color_abi_version(void) { return SN_MESH_COLOR_ABI_VERSION; }
-
-constexpr size_t kMeshShadeOptsMin = sizeof(SnMeshShadeOpts);  // the first layout
-
-size_t sn_mesh_color_workspace_bytes(int64_t n_triangles, int32_t height, int32_t width) {
-    return sn_mesh_workspace_bytes(n_triangles, height, width);
-}
-
-// SnMeshShadeOpts (adopted) -> the kernels' SnMeshShade; false: a component is not finite
-static bool fill_mesh_shade(const SnMeshShadeOpts& so, const uint8_t* vertex_colors, SnMeshShade& s) {
-    s.vertex_colors = vertex_colors;
-    for (int c = 0; c < 3; ++c) {
-        if (!std::isfinite(so.base_color[c]) || !std::isfinite(so.ambient[c]) || !std::isfinite(so.background[c])) return false;
-        s.base[c] = so.base_color[c];
-        s.ambient[c] = so.ambient[c];
-        s.background[c] = so.background[c];
-    }
-    s.gamma = so.gamma != 0;
-    return true;
-}
-
-int sn_mesh_raster_color(const float* vertices, int64_t n_vertices, const uint8_t* vertex_colors, const int32_t* triangles,
-                         int64_t n_triangles, const float* model_view, float fx, float fy, float cx, float cy, int32_t height, int32_t width,
-                         const SnMeshRasterOpts* opts, const SnMeshShadeOpts* shade, float* depth, uint8_t* color, void* workspace,
-                         size_t workspace_bytes, SnStream stream) {
-    const std::string who = "sn_mesh_raster_color";
-    SnMeshColorParams cp;
-    memset(&cp, 0, sizeof(cp));
-    if (int rc = begin_raster(who, shade && color, vertices, n_vertices, triangles, n_triangles, model_view, fx, fy, cx, cy, height, width, opts,
-                              depth, workspace, workspace_bytes, cp.r))
-        return rc;
-    SnMeshShadeOpts so;
-    if (int rc = adopt_struct(nullptr, shade, kMeshShadeOptsMin, so, "sn_mesh_raster_color: SnMeshShadeOpts")) return rc;
-    if (!fill_mesh_shade(so, vertex_colors, cp.s))
-        return fail(nullptr, SN_ERR_INVALID, "sn_mesh_raster_color: base_color, ambient and background must be finite");
-    cp.color = color;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sn_mesh_tile_color_kernel, launch_mesh_setup(cp.r, st), dim3(SN_MESH_BATCH), 0, st, cp);
-    return end_launches(who);
-}
-
-int sn_aabb_mask_condition_combined(const float* origins, const float* directions, const float* depth, int32_t height, int32_t width,
-                                    const float* aabb, const SnMaskOpts* opts, const float* mesh_depth, const uint8_t* mesh_color,
-                                    uint8_t* mask, float* condition, void* workspace, size_t workspace_bytes, SnStream stream) {
-    const std::string who = "sn_aabb_mask_condition_combined";
-    if (!origins || !directions || !depth || !aabb || !opts || !mesh_depth || !mesh_color || !mask || height <= 0 || width <= 0)
-        return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    const size_t n = (size_t)height * width;
-    SnCombinedMaskParams cp;
-    SnMaskParams& p = cp.m;
-    if (int rc = begin_mask_step(who, opts, depth, height, width, mask, condition, workspace, workspace_bytes, st, p)) return rc;
-    p.origins = origins;
-    p.directions = directions;
-    memcpy(p.aabb, aabb, sizeof(p.aabb));
-    cp.mesh_depth = mesh_depth;
-    cp.mesh_color = mesh_color;
-    hipLaunchKernelGGL(sn_mask_visible_kernel, mask_visible_grid(n), dim3(256), 0, st, p);
-    if (p.dilate) hipLaunchKernelGGL(sn_mask_prefix_kernel, dim3((unsigned)height), dim3(64), 0, st, p);
-    hipLaunchKernelGGL(sn_mask_condition_combined_kernel, per_pixel_grid(n), dim3(256), 0, st, cp);
-    return end_launches(who);
-}
-
-
-// ---- include/signerf_hip_mesh_rays.h: the mesh along the camera's own rays -----------------------------------------------------------
-int sn_mesh_rays_abi_version(void) { return SN_MESH_RAYS_ABI_VERSION; }
-
-constexpr size_t kMeshRaysOptsMin = sizeof(SnMeshRaysOpts);  // the first layout
-#define SN_MESH_RAYS_MAX_TRIS ((int64_t)1 << 26)  // a leaf reference packs first * 8 + count into 31 bits
-
-size_t sn_mesh_accel_bytes(int64_t n_triangles) {
-    if (n_triangles < 0 || n_triangles > SN_MESH_RAYS_MAX_TRIS) return 0;
-    const size_t f = (size_t)n_triangles;
-    return sizeof(SnMeshAccelHeader) + std::max<size_t>(f, 1) * sizeof(SnMeshAccelNode) + f * sizeof(SnMeshAccelTri);
-}
-
-// What the two ray casts share, for the entry point `who`: the checks of the rays, the blob, SnMeshRaysOpts and (with a colour image)
-// SnMeshShadeOpts, and the SnMeshRaysParams.
-static int begin_cast_rays(const std::string& who, const float* origins, const float* directions, int32_t height, int32_t width,
-                           const float* forward, const void* accel, size_t accel_bytes, const int32_t* triangles, int64_t n_triangles,
-                           const uint8_t* vertex_colors, int64_t n_vertices, const SnMeshRaysOpts* opts, const SnMeshShadeOpts* shade,
-                           float* depth, uint8_t* color, bool need_triangles, SnMeshRaysParams& p) {
-    if (!origins || !directions || !forward || !accel || !opts || !depth || height <= 0 || width <= 0 || height > SN_MESH_MAX_DIM ||
-        width > SN_MESH_MAX_DIM || n_triangles < 0 || n_triangles > SN_MESH_RAYS_MAX_TRIS || n_vertices < 0 ||
-        (color && (!shade || (need_triangles && !triangles))))
-        return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
-    SnMeshRaysOpts o;
-    if (int rc = adopt_struct(nullptr, opts, kMeshRaysOptsMin, o, (who + ": SnMeshRaysOpts").c_str())) return rc;
-    if (!(o.znear > 0.0f) || !(o.zfar > o.znear) || !std::isfinite(o.zfar)) return fail(nullptr, SN_ERR_INVALID, who + ": need 0 < znear < zfar < inf");
-    if (accel_bytes != sn_mesh_accel_bytes(n_triangles) || ((uintptr_t)accel & 15u) != 0)
-        return fail(nullptr, SN_ERR_INVALID, who + ": accel must be a 16-byte-aligned blob of sn_mesh_accel_bytes(n_triangles) bytes");
-    const double fn = std::sqrt((double)forward[0] * forward[0] + (double)forward[1] * forward[1] + (double)forward[2] * forward[2]);
-    if (!std::isfinite(fn) || !(fn > 0.0)) return fail(nullptr, SN_ERR_INVALID, who + ": forward must be a finite non-zero vector");
-    memset(&p, 0, sizeof(p));
-    if (color) {
-        SnMeshShadeOpts so;
-        if (int rc = adopt_struct(nullptr, shade, kMeshShadeOptsMin, so, (who + ": SnMeshShadeOpts").c_str())) return rc;
-        if (!fill_mesh_shade(so, vertex_colors, p.s)) return fail(nullptr, SN_ERR_INVALID, who + ": base_color, ambient and background must be finite");
-    }
-    p.origins = origins;
-    p.directions = directions;
-    p.height = height;
-    p.width = width;
-    for (int k = 0; k < 3; ++k) p.fwd[k] = (float)(forward[k] / fn);
-    p.znear = o.znear;
-    p.zfar = o.zfar;
-    p.cull = o.cull_back_faces != 0;
-    p.accel = (const uint8_t*)accel;
-    p.n_tris = (int32_t)n_triangles;
-    p.tris = triangles;
-    p.n_vertices = n_vertices;
-    p.depth = depth;
-    p.color = color;
-    return SN_OK;
-}
-
-static dim3 cast_rays_grid(int32_t height, int32_t width) { return dim3((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16)); }
-
-int sn_mesh_cast_rays(const float* origins, const float* directions, int32_t height, int32_t width, const float* forward,
-                      const void* accel, size_t accel_bytes, const int32_t* triangles, int64_t n_triangles, const uint8_t* vertex_colors,
-                      int64_t n_vertices, const SnMeshRaysOpts* opts, const SnMeshShadeOpts* shade, float* depth, uint8_t* color,
-                      SnStream stream) {
-    const std::string who = "sn_mesh_cast_rays";
-    SnMeshRaysParams p;
-    if (int rc = begin_cast_rays(who, origins, directions, height, width, forward, accel, accel_bytes, triangles, n_triangles, vertex_colors,
-                                 n_vertices, opts, shade, depth, color, true, p))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (color)
-        hipLaunchKernelGGL(sn_mesh_rays_kernel<true>, cast_rays_grid(height, width), dim3(SN_RAYS_BLOCK), 0, st, p);
-    else
-        hipLaunchKernelGGL(sn_mesh_rays_kernel<false>, cast_rays_grid(height, width), dim3(SN_RAYS_BLOCK), 0, st, p);
-    return end_launches(who);
-}
-
-
-// ---- include/signerf_hip_mesh_material.h: the mesh's colour image shaded with its materials -------------------------------------------
-int sn_mesh_material_abi_version(void) { return SN_MESH_MATERIAL_ABI_VERSION; }
-
-constexpr size_t kMeshMaterialsMin = sizeof(SnMeshMaterials);  // the first layout
-static_assert(sizeof(SnMeshMaterial) == sizeof(SnMeshMaterialRec), "the public record is the kernels' record");
-
-// SnMeshMaterials (checked against its host copy of the records) -> the kernels' SnMeshMaterialSet
-static int adopt_materials(const std::string& who, const SnMeshMaterials* materials, int64_t n_triangles, SnMeshMaterialSet& m) {
-    if (!materials) return fail(nullptr, SN_ERR_INVALID, who + ": materials is NULL");
-    SnMeshMaterials a;
-    if (int rc = adopt_struct(nullptr, materials, kMeshMaterialsMin, a, (who + ": SnMeshMaterials").c_str())) return rc;
-    if (a.n_materials < 1 || a.n_materials > 65535) return fail(nullptr, SN_ERR_INVALID, who + ": n_materials must be in [1, 65535]");
-    if (!a.materials || !a.host_materials || (n_triangles > 0 && !a.triangle_material))
-        return fail(nullptr, SN_ERR_INVALID, who + ": materials, host_materials and triangle_material must not be NULL");
-    if (((uintptr_t)a.materials & 15u) != 0 || ((uintptr_t)a.corner_uv & 7u) != 0 || ((uintptr_t)a.texels & 3u) != 0)
-        return fail(nullptr, SN_ERR_INVALID, who + ": materials must be 16-byte, corner_uv 8-byte and texels 4-byte aligned");
-    if (a.texel_bytes > 0 && !a.texels) return fail(nullptr, SN_ERR_INVALID, who + ": texels is NULL but texel_bytes is not 0");
-    const uint64_t n_texels = a.texel_bytes / 4u;
-    for (int32_t k = 0; k < a.n_materials; ++k) {
-        const SnMeshMaterial& r = a.host_materials[k];
-        const std::string which = who + ": material " + std::to_string(k);
-        for (int c = 0; c < 4; ++c)
-            if (!std::isfinite(r.base_color[c])) return fail(nullptr, SN_ERR_INVALID, which + ": base_color must be finite");
-        if (r.tex_width == 0 && r.tex_height == 0) continue;
-        if (r.tex_width < 1 || r.tex_height < 1 || r.tex_width > SN_MATERIAL_MAX_SIDE || r.tex_height > SN_MATERIAL_MAX_SIDE)
-            return fail(nullptr, SN_ERR_INVALID, which + ": a texture side must be in [1, 16384] (or both 0: no texture)");
-        if ((uint64_t)r.texel_offset + (uint64_t)r.tex_width * (uint64_t)r.tex_height > n_texels)
-            return fail(nullptr, SN_ERR_INVALID, which + ": its texture ends beyond the texel blob (texel_bytes too small)");
-    }
-    m.materials = (const SnMeshMaterialRec*)a.materials;
-    m.triangle_material = a.triangle_material;
-    m.corner_uv = a.corner_uv;
-    m.texels = (const uint32_t*)a.texels;
-    m.n_texels = n_texels;
-    m.n_materials = a.n_materials;
-    m.texture_srgb = a.texture_srgb != 0;
-    return SN_OK;
-}
-
-int sn_mesh_raster_color_materials(const float* vertices, int64_t n_vertices, const SnMeshMaterials* materials, const int32_t* triangles,
-                                   int64_t n_triangles, const float* model_view, float fx, float fy, float cx, float cy, int32_t height,
-                                   int32_t width, const SnMeshRasterOpts* opts, const SnMeshShadeOpts* shade, float* depth, uint8_t* color,
-                                   void* workspace, size_t workspace_bytes, SnStream stream) {
-    const std::string who = "sn_mesh_raster_color_materials";
-    SnMeshMaterialColorParams cp;
-    memset(&cp, 0, sizeof(cp));
-    if (n_triangles < 0) return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
-    if (int rc = adopt_materials(who, materials, n_triangles, cp.m)) return rc;
-    SnMeshShadeOpts so;
-    if (!shade) return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
-    if (int rc = adopt_struct(nullptr, shade, kMeshShadeOptsMin, so, (who + ": SnMeshShadeOpts").c_str())) return rc;
-    if (!fill_mesh_shade(so, nullptr, cp.s)) return fail(nullptr, SN_ERR_INVALID, who + ": base_color, ambient and background must be finite");
-    if (int rc = begin_raster(who, color != nullptr, vertices, n_vertices, triangles, n_triangles, model_view, fx, fy, cx, cy, height, width, opts,
-                              depth, workspace, workspace_bytes, cp.r))
-        return rc;
-    cp.color = color;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sn_mesh_tile_material_kernel, launch_mesh_setup(cp.r, st), dim3(SN_MESH_BATCH), 0, st, cp);
-    return end_launches(who);
-}
-
-int sn_mesh_cast_rays_materials(const float* origins, const float* directions, int32_t height, int32_t width, const float* forward,
-                                const void* accel, size_t accel_bytes, const int32_t* triangles, int64_t n_triangles,
-                                const SnMeshMaterials* materials, int64_t n_vertices, const SnMeshRaysOpts* opts, const SnMeshShadeOpts* shade,
-                                float* depth, uint8_t* color, SnStream stream) {
-    const std::string who = "sn_mesh_cast_rays_materials";
-    SnMeshMaterialRaysParams mp;
-    memset(&mp, 0, sizeof(mp));
-    if (!color || !shade || n_triangles < 0) return fail(nullptr, SN_ERR_INVALID, who + ": bad argument");
-    if (int rc = adopt_materials(who, materials, n_triangles, mp.m)) return rc;
-    if (int rc = begin_cast_rays(who, origins, directions, height, width, forward, accel, accel_bytes, triangles, n_triangles, nullptr, n_vertices,
-                                 opts, shade, depth, color, false, mp.r))
-        return rc;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sn_mesh_rays_material_kernel, cast_rays_grid(height, width), dim3(SN_RAYS_BLOCK), 0, st, mp);
-    return end_launches(who);
-}
-
-
-// ---- include/signerf_hip_ray_batch.h: rays of many cameras in one launch ---------------------------------------------------------------
-int sn_ray_batch_abi_version(void) { return SN_RAY_BATCH_ABI_VERSION; }
-
-int sn_generate_ray_batch(const SnCameraDesc* cameras, int32_t n_cameras, const int64_t* ray_indices, const int64_t* camera_indices,
-                          const float* coords, int64_t n, float* origins, float* directions, float* pixel_area, float* directions_norm,
-                          const float* aabb, float* nears, float* fars, const uint8_t* images, int32_t img_h, int32_t img_w,
-                          int32_t img_c, float* pixels, SnStream stream) {
-    const std::string who = "sn_generate_ray_batch";
-    if (!cameras || n_cameras < 1 || n < 0) return fail(nullptr, SN_ERR_INVALID, who + ": bad argument (cameras, n_cameras >= 1, n >= 0)");
-    const bool triplets = ray_indices != nullptr, pairs = camera_indices != nullptr || coords != nullptr;
-    if (triplets == pairs)
-        return fail(nullptr, SN_ERR_INVALID, who + ": give exactly one index form, ray_indices [n,3] or camera_indices [n] with coords [n,2]");
-    if (pairs && (!camera_indices || !coords)) return fail(nullptr, SN_ERR_INVALID, who + ": camera_indices and coords go together");
-    if ((images != nullptr) != (pixels != nullptr)) return fail(nullptr, SN_ERR_INVALID, who + ": images and pixels go together");
-    if (images) {
-        if (!triplets) return fail(nullptr, SN_ERR_INVALID, who + ": pixels are gathered with the ray_indices form only");
-        if (img_h < 1 || img_w < 1 || img_c < 1 || img_c > 4)
-            return fail(nullptr, SN_ERR_INVALID, who + ": the image stack needs img_h, img_w >= 1 and img_c in 1..4");
-    }
-    if (n == 0) return SN_OK;
-    SnRayBatchParams p;
-    memset(&p, 0, sizeof(p));
-    p.cameras = cameras;
-    p.n_cameras = n_cameras;
-    p.ray_indices = ray_indices;
-    p.camera_indices = camera_indices;
-    p.coords = coords;
-    p.n = n;
-    p.origins = origins;
-    p.directions = directions;
-    p.pixel_area = pixel_area;
-    p.directions_norm = directions_norm;
-    p.has_aabb = aabb != nullptr;
-    if (aabb) memcpy(p.aabb, aabb, sizeof(p.aabb));
-    p.nears = nears;
-    p.fars = fars;
-    p.images = images;
-    p.img_h = img_h;
-    p.img_w = img_w;
-    p.img_c = img_c;
-    p.pixels = pixels;
-    if ((n + 255) / 256 > 0x7fffffffll) return fail(nullptr, SN_ERR_INVALID, who + ": n exceeds the grid (2^31 - 1 blocks of 256 rays)");
-    hipLaunchKernelGGL(sn_ray_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
-    return end_launches(who);
-}
-
-// ---- include/signerf_hip_png.h: a device uint8 image to the bytes of its .png file ----------------------------------------------------------
-int sn_png_abi_version(void) { return SN_PNG_ABI_VERSION; }
-size_t sn_png_segment_bytes(void) { return SN_PNG_SEGMENT_BYTES; }
-size_t sn_png_max_file_bytes(int32_t h, int32_t w, int32_t c) {
-    return sn_png_shape_ok(h, w, c) ? (size_t)sn_png_file_bound((uint32_t)h, (uint32_t)w, (uint32_t)c) : 0;
-}
-size_t sn_png_workspace_bytes(int32_t h, int32_t w, int32_t c) {
-    return sn_png_shape_ok(h, w, c) ? (size_t)sn_png_workspace_size((uint32_t)h, (uint32_t)w, (uint32_t)c) : 0;
-}
-
-int sn_png_encode(const uint8_t* image, int32_t h, int32_t w, int32_t c, void* workspace, size_t workspace_bytes, uint8_t* file,
-                  size_t file_capacity, uint64_t* file_bytes, SnStream stream) {
-    const std::string who = "sn_png_encode";
-    if (!image || !workspace || !file || !file_bytes) return fail(nullptr, SN_ERR_INVALID, who + ": NULL argument (image, workspace, file, file_bytes)");
-    if (c != 1 && c != 3) return fail(nullptr, SN_ERR_INVALID, who + ": c must be 1 (greyscale) or 3 (RGB)");
-    if (!sn_png_shape_ok(h, w, c)) return fail(nullptr, SN_ERR_INVALID, who + ": h and w must lie in 1..8192");
-    if (workspace_bytes < sn_png_workspace_bytes(h, w, c) || ((uintptr_t)workspace & 15u))
-        return fail(nullptr, SN_ERR_INVALID, who + ": workspace below sn_png_workspace_bytes, or not 16-byte aligned");
-    if (file_capacity < sn_png_max_file_bytes(h, w, c)) return fail(nullptr, SN_ERR_INVALID, who + ": file_capacity below sn_png_max_file_bytes");
-    SnPngParams p;
-    memset(&p, 0, sizeof(p));
-    p.image = image;
-    p.h = (uint32_t)h;
-    p.w = (uint32_t)w;
-    p.c = (uint32_t)c;
-    p.row_bytes = p.w * p.c;
-    p.stride = 1 + p.row_bytes;
-    p.stream_bytes = (uint32_t)sn_png_stream_bytes(p.h, p.w, p.c);
-    p.nseg = sn_png_segment_count(p.stream_bytes);
-    uint8_t* ws = (uint8_t*)workspace;   // slots (a multiple of 16 bytes each), the offsets, then the 4 uint32 arrays
-    p.slots = ws;
-    ws += (size_t)p.nseg * SN_PNG_SLOT_STRIDE;
-    p.seg_off = (uint64_t*)ws;
-    ws += (size_t)p.nseg * 8;
-    p.seg_bytes = (uint32_t*)ws;
-    p.seg_crc = p.seg_bytes + p.nseg;
-    p.seg_adler = p.seg_crc + p.nseg;
-    p.file = file;
-    p.file_bytes = file_bytes;
-    hipStream_t st = (hipStream_t)stream;
-    if (c == 1) hipLaunchKernelGGL(sn_png_segment_deflate_kernel<1>, dim3(p.nseg), dim3(64), 0, st, p);
-    else hipLaunchKernelGGL(sn_png_segment_deflate_kernel<3>, dim3(p.nseg), dim3(64), 0, st, p);
-    hipLaunchKernelGGL(sn_png_finish_file_kernel, dim3(1), dim3(1024), 0, st, p);
-    hipLaunchKernelGGL(sn_png_compact_bytes_kernel, dim3(p.nseg), dim3(256), 0, st, p);
-    return end_launches(who);
-}
-
-// ---- include/signerf_hip_losses.h: differentiable compositing and the sampler losses, one wave per ray ------------------------------------
-int sn_losses_abi_version(void) { return SN_LOSSES_ABI_VERSION; }
-static_assert(SN_LOSSES_MAX_SAMPLES == SN_LOSS_MAX_S, "the header's sample limit is the kernels'");
-
-// the checks every entry point shares; 1 = go on and launch, 0 = R == 0 (SN_OK, nothing to do), < 0 = refused (-status)
-static int losses_prologue(const std::string& who, int64_t R, int32_t S, int32_t P, bool pointers_ok, const char* pointers) {
-    if (R < 0) return -fail(nullptr, SN_ERR_INVALID, who + ": R must be >= 0");
-    if (S < 1 || S > SN_LOSS_MAX_S) return -fail(nullptr, SN_ERR_INVALID, who + ": S must lie in 1.." + std::to_string(SN_LOSS_MAX_S));
-    if (P < 1 || P > SN_LOSS_MAX_S) return -fail(nullptr, SN_ERR_INVALID, who + ": P must lie in 1.." + std::to_string(SN_LOSS_MAX_S));
-    if (R == 0) return 0;   // (an empty tensor's pointer may be NULL)
-    if (!pointers_ok) return -fail(nullptr, SN_ERR_INVALID, who + ": NULL argument (" + pointers + ")");
-    if (R > 0x7fffffffll) return -fail(nullptr, SN_ERR_INVALID, who + ": R exceeds the grid (2^31 - 1 rays)");
-    return 1;
-}
-
-int sn_loss_composite_forward(const float* deltas, const float* density, const float* colour, const float* background, int64_t R, int32_t S,
-                              float* weights, float* rgb, float* accumulation, SnStream stream) {
-    const std::string who = "sn_loss_composite_forward";
-    const bool ok = deltas && density && (weights || rgb || accumulation) && (colour || !rgb);
-    const int go = losses_prologue(who, R, S, 1, ok, "deltas, density; one output at least; colour with rgb");
-    if (go <= 0) return -go;
-    SnLossCompositeParams p;
-    memset(&p, 0, sizeof(p));
-    p.deltas = deltas;
-    p.density = density;
-    p.colour = colour;
-    p.background = background;
-    p.S = S;
-    p.weights = weights;
-    p.rgb = rgb;
-    p.accumulation = accumulation;
-    hipLaunchKernelGGL(sn_loss_composite_forward_kernel, dim3((unsigned)R), dim3(64), 0, (hipStream_t)stream, p);
-    return end_launches(who);
-}
-
-int sn_loss_composite_backward(const float* deltas, const float* density, const float* colour, const float* background, int64_t R, int32_t S,
-                               const float* grad_weights, const float* grad_rgb, const float* grad_acc, float* grad_density,
-                               float* grad_colour, SnStream stream) {
-    const std::string who = "sn_loss_composite_backward";
-    const bool ok = deltas && density && grad_density && (colour || (!grad_rgb && !grad_colour));
-    const int go = losses_prologue(who, R, S, 1, ok, "deltas, density, grad_density; colour with grad_rgb or grad_colour");
-    if (go <= 0) return -go;
-    SnLossCompositeParams p;
-    memset(&p, 0, sizeof(p));
-    p.deltas = deltas;
-    p.density = density;
-    p.colour = colour;
-    p.background = background;
-    p.S = S;
-    p.grad_weights = grad_weights;
-    p.grad_rgb = grad_rgb;
-    p.grad_acc = grad_acc;
-    p.grad_density = grad_density;
-    p.grad_colour = grad_colour;
-    hipLaunchKernelGGL(sn_loss_composite_backward_kernel, dim3((unsigned)R), dim3(64), 0, (hipStream_t)stream, p);
-    return end_launches(who);
-}
-
-int sn_loss_distortion_forward(const float* t, const float* w, int64_t R, int32_t S, float* loss, SnStream stream) {
-    const std::string who = "sn_loss_distortion_forward";
-    const int go = losses_prologue(who, R, S, 1, t && w && loss, "t, w, loss");
-    if (go <= 0) return -go;
-    SnLossDistortionParams p;
-    memset(&p, 0, sizeof(p));
-    p.t = t;
-    p.w = w;
-    p.S = S;
-    p.loss = loss;
-    hipLaunchKernelGGL(sn_loss_distortion_forward_kernel, dim3((unsigned)R), dim3(64), sn_loss_distortion_lds(S), (hipStream_t)stream, p);
-    return end_launches(who);
-}
-
-int sn_loss_distortion_backward(const float* t, const float* w, const float* grad_loss, int64_t R, int32_t S, float* grad_w, SnStream stream) {
-    const std::string who = "sn_loss_distortion_backward";
-    const int go = losses_prologue(who, R, S, 1, t && w && grad_loss && grad_w, "t, w, grad_loss, grad_w");
-    if (go <= 0) return -go;
-    SnLossDistortionParams p;
-    memset(&p, 0, sizeof(p));
-    p.t = t;
-    p.w = w;
-    p.grad_loss = grad_loss;
-    p.S = S;
-    p.grad_w = grad_w;
-    hipLaunchKernelGGL(sn_loss_distortion_backward_kernel, dim3((unsigned)R), dim3(64), sn_loss_distortion_lds(S), (hipStream_t)stream, p);
-    return end_launches(who);
-}
-
-int sn_loss_interlevel_forward(const float* t, const float* w, const float* t_env, const float* w_env, int64_t R, int32_t S, int32_t P,
-                               float* loss, float* w_outer, SnStream stream) {
-    const std::string who = "sn_loss_interlevel_forward";
-    const int go = losses_prologue(who, R, S, P, t && t_env && w_env && (loss || w_outer) && (w || !loss),
-                                   "t, t_env, w_env; loss or w_outer; w with loss");
-    if (go <= 0) return -go;
-    SnLossInterlevelParams p;
-    memset(&p, 0, sizeof(p));
-    p.t = t;
-    p.w = w;
-    p.t_env = t_env;
-    p.w_env = w_env;
-    p.S = S;
-    p.P = P;
-    p.loss = loss;
-    p.w_outer = w_outer;
-    hipLaunchKernelGGL(sn_loss_interlevel_forward_kernel, dim3((unsigned)R), dim3(64), sn_loss_interlevel_lds(S, P, false), (hipStream_t)stream, p);
-    return end_launches(who);
-}
-
-int sn_loss_interlevel_backward(const float* t, const float* w, const float* t_env, const float* w_env, const float* grad_loss, int64_t R,
-                                int32_t S, int32_t P, float* grad_w_env, SnStream stream) {
-    const std::string who = "sn_loss_interlevel_backward";
-    const int go = losses_prologue(who, R, S, P, t && w && t_env && w_env && grad_loss && grad_w_env, "t, w, t_env, w_env, grad_loss, grad_w_env");
-    if (go <= 0) return -go;
-    SnLossInterlevelParams p;
-    memset(&p, 0, sizeof(p));
-    p.t = t;
-    p.w = w;
-    p.t_env = t_env;
-    p.w_env = w_env;
-    p.grad_loss = grad_loss;
-    p.S = S;
-    p.P = P;
-    p.grad_w_env = grad_w_env;
-    hipLaunchKernelGGL(sn_loss_interlevel_backward_kernel, dim3((unsigned)R), dim3(64), sn_loss_interlevel_lds(S, P, true), (hipStream_t)stream, p);
-    return end_launches(who);
-}
-
-int sn_tensor_to_uint8(const float* in, int64_t n, uint8_t* out, SnStream stream) {
-    if (!in || !out || n < 0) return fail(nullptr, SN_ERR_INVALID, "sn_tensor_to_uint8: bad argument");
-    if (n == 0) return SN_OK;
-    hipLaunchKernelGGL(sn_tensor_to_uint8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, in, n, out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_tensor_to_uint8 launch: ") + hipGetErrorString(e));
-    return SN_OK;
-}
-
-int sn_resize_bilinear(const void* src, int32_t src_u8, int32_t src_h, int32_t src_w, int64_t src_row_stride, int32_t channels, float* dst,
-                       int32_t dst_h, int32_t dst_w, int64_t dst_row_stride, int32_t threshold, SnStream stream) {
-    if (!src || !dst || src_h < 1 || src_w < 1 || dst_h < 1 || dst_w < 1 || channels < 1 ||
-        src_row_stride < (int64_t)src_w * channels || dst_row_stride < (int64_t)dst_w * channels)
-        return fail(nullptr, SN_ERR_INVALID, "sn_resize_bilinear: bad argument");
-    SnResizeParams p;
-    p.src = src;
-    p.dst = dst;
-    p.src_u8 = src_u8 != 0;
-    p.src_h = src_h;
-    p.src_w = src_w;
-    p.dst_h = dst_h;
-    p.dst_w = dst_w;
-    p.channels = channels;
-    p.src_row_stride = src_row_stride;
-    p.dst_row_stride = dst_row_stride;
-    p.threshold = threshold != 0;
-    const int64_t n = (int64_t)dst_h * dst_w * channels;
-    hipLaunchKernelGGL(sn_resize_bilinear_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, SN_ERR_HIP, std::string("sn_resize_bilinear launch: ") + hipGetErrorString(e));
-    return SN_OK;
-}
-
 }  // extern "C"
+
+// the entry points that take no handle
+#include "sn_api_rays.h"
+#include "sn_api_stages.h"
+#include "sn_api_mask.h"
+#include "sn_api_mesh.h"
+#include "sn_api_png.h"
+#include "sn_api_losses.h"

@@ -350,22 +350,38 @@ def _raster_args(mv, znear: float, zfar: float, cull_back_faces: bool):
     return opts, (C.c_float * 12)(*np.asarray(mv, dtype=np.float64).reshape(12).tolist())
 
 
-def raster_depth(vertices: Tensor, triangles: Tensor, mv, fx: float, fy: float, cx: float, cy: float, height: int, width: int,
-                 znear: float = ZNEAR, zfar: float = ZFAR, cull_back_faces: bool = True, out: Optional[Tensor] = None) -> Tensor:
-    """``sn_mesh_raster_depth``: vertices [V,3] fp32 / triangles [F,3] int32 on the GPU, mv: camera-from-object [3,4] (host) ->
-    z-depth [H,W,1] fp32 on the GPU, 0 where the mesh is not drawn."""
+def _raster(fn: str, vertices: Tensor, triangles: Tensor, mv, fx, fy, cx, cy, height, width, znear, zfar, cull_back_faces, depth,
+            colors=None, shade=None) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """One call of the raster `fn` -> (color, depth).  depth: True allocates the image, a tensor is written in place, None passes NULL.
+    With `shade` (the colour rasters) the colour image is allocated and `colors` -- vertex colours or None, or ``MeshMaterials`` -- goes
+    with the mesh; without it color is None."""
     lib = _lib.load()
     dev = vertices.device
     opts, m = _raster_args(mv, znear, zfar, cull_back_faces)
     F = int(triangles.shape[0])
+    ws_bytes = lib.sn_mesh_workspace_bytes if shade is None else lib.sn_mesh_color_workspace_bytes
     with torch.cuda.device(dev):
-        depth = out if out is not None else torch.empty((height, width, 1), dtype=torch.float32, device=dev)
-        ws = torch.empty(max(lib.sn_mesh_workspace_bytes(F, height, width), 1), dtype=torch.uint8, device=dev)
-        _lib.check(lib.sn_mesh_raster_depth(_lib.ptr(vertices), int(vertices.shape[0]), _lib.ptr(triangles), F, m, float(fx), float(fy),
-                                            float(cx), float(cy), int(height), int(width), C.byref(opts), _lib.ptr(depth), ws.data_ptr(),
-                                            ws.numel(), _lib.current_stream()),
-                   None, "sn_mesh_raster_depth")
-    return depth
+        color, tint, lit = None, [], []
+        if shade is not None:
+            held = colors.struct(dev) if isinstance(colors, MeshMaterials) else None if colors is None else colors.contiguous()
+            tint, lit = [C.byref(held) if isinstance(colors, MeshMaterials) else _lib.ptr(held)], [C.byref(shade)]
+            color = torch.empty((height, width, 3), dtype=torch.uint8, device=dev)
+        if depth is True:
+            depth = torch.empty((height, width, 1), dtype=torch.float32, device=dev)
+        ws = torch.empty(max(ws_bytes(F, height, width), 1), dtype=torch.uint8, device=dev)
+        _lib.check(getattr(lib, fn)(_lib.ptr(vertices), int(vertices.shape[0]), *tint, _lib.ptr(triangles), F, m, float(fx), float(fy), float(cx),
+                                    float(cy), int(height), int(width), C.byref(opts), *lit, _lib.ptr(depth), *([_lib.ptr(color)] if lit else []),
+                                    ws.data_ptr(), ws.numel(), _lib.current_stream()),
+                   None, fn)
+    return color, depth
+
+
+def raster_depth(vertices: Tensor, triangles: Tensor, mv, fx: float, fy: float, cx: float, cy: float, height: int, width: int,
+                 znear: float = ZNEAR, zfar: float = ZFAR, cull_back_faces: bool = True, out: Optional[Tensor] = None) -> Tensor:
+    """``sn_mesh_raster_depth``: vertices [V,3] fp32 / triangles [F,3] int32 on the GPU, mv: camera-from-object [3,4] (host) ->
+    z-depth [H,W,1] fp32 on the GPU, 0 where the mesh is not drawn."""
+    return _raster("sn_mesh_raster_depth", vertices, triangles, mv, fx, fy, cx, cy, height, width, znear, zfar, cull_back_faces,
+                   out if out is not None else True)[1]
 
 
 # pyrender's mesh shader under the reference's Scene(ambient_light=[1, 1, 1]) with no other light, as recalled from pyrender 0.1.45 --
@@ -493,24 +509,11 @@ def raster_color_materials(vertices: Tensor, triangles: Tensor, mv, fx: float, f
                            cull_back_faces: bool = True, with_depth: bool = True) -> Tuple[Tensor, Optional[Tensor]]:
     """``sn_mesh_raster_color_materials``: ``raster_color`` with `materials` in place of the vertex colours; base_color is the default
     material (a triangle whose material index is outside the records).  The depth is bit-identical to ``raster_depth``'s."""
-    lib = _lib.load()
-    dev = vertices.device
     F = int(triangles.shape[0])
     if int(materials.triangle_material.shape[0]) != F:
         raise ValueError(f"the materials are those of {int(materials.triangle_material.shape[0])} triangles, the mesh has {F}")
-    opts, m = _raster_args(mv, znear, zfar, cull_back_faces)
-    shade = _shade_opts(base_color, ambient, background, gamma)
-    with torch.cuda.device(dev):
-        mats = materials.struct(dev)
-        color = torch.empty((height, width, 3), dtype=torch.uint8, device=dev)
-        depth = torch.empty((height, width, 1), dtype=torch.float32, device=dev) if with_depth else None
-        ws = torch.empty(max(lib.sn_mesh_color_workspace_bytes(F, height, width), 1), dtype=torch.uint8, device=dev)
-        _lib.check(lib.sn_mesh_raster_color_materials(_lib.ptr(vertices), int(vertices.shape[0]), C.byref(mats), _lib.ptr(triangles), F, m,
-                                                      float(fx), float(fy), float(cx), float(cy), int(height), int(width), C.byref(opts),
-                                                      C.byref(shade), _lib.ptr(depth), _lib.ptr(color), ws.data_ptr(), ws.numel(),
-                                                      _lib.current_stream()),
-                   None, "sn_mesh_raster_color_materials")
-    return color, depth
+    return _raster("sn_mesh_raster_color_materials", vertices, triangles, mv, fx, fy, cx, cy, height, width, znear, zfar, cull_back_faces,
+                   True if with_depth else None, materials, _shade_opts(base_color, ambient, background, gamma))
 
 
 def raster_color(vertices: Tensor, triangles: Tensor, mv, fx: float, fy: float, cx: float, cy: float, height: int, width: int,
@@ -520,28 +523,11 @@ def raster_color(vertices: Tensor, triangles: Tensor, mv, fx: float, fy: float, 
     """``sn_mesh_raster_color``: as ``raster_depth``, plus vertex_colors [V,4] uint8 RGBA on the GPU (or None) and the shading
     (``shade_defaults``) -> (color [H,W,3] uint8, depth [H,W,1] fp32 or None) on the GPU.  The depth is bit-identical to
     ``raster_depth``'s."""
-    lib = _lib.load()
-    dev = vertices.device
     if vertex_colors is not None and (vertex_colors.dtype != torch.uint8 or tuple(vertex_colors.shape) != (int(vertices.shape[0]), 4)):
         raise ValueError(f"vertex_colors must be [V,4] uint8 with V = {int(vertices.shape[0])}, got {tuple(vertex_colors.shape)} "
                          f"{vertex_colors.dtype}")
-    opts, m = _raster_args(mv, znear, zfar, cull_back_faces)
-    shade = _lib.SnMeshShadeOpts()
-    shade.base_color[:] = [float(x) for x in base_color]
-    shade.ambient[:] = [float(x) for x in ambient]
-    shade.background[:] = [float(x) for x in background]
-    shade.gamma = int(bool(gamma))
-    F = int(triangles.shape[0])
-    with torch.cuda.device(dev):
-        color = torch.empty((height, width, 3), dtype=torch.uint8, device=dev)
-        depth = torch.empty((height, width, 1), dtype=torch.float32, device=dev) if with_depth else None
-        ws = torch.empty(max(lib.sn_mesh_color_workspace_bytes(F, height, width), 1), dtype=torch.uint8, device=dev)
-        vc = None if vertex_colors is None else vertex_colors.contiguous()
-        _lib.check(lib.sn_mesh_raster_color(_lib.ptr(vertices), int(vertices.shape[0]), _lib.ptr(vc), _lib.ptr(triangles), F, m, float(fx),
-                                            float(fy), float(cx), float(cy), int(height), int(width), C.byref(opts), C.byref(shade),
-                                            _lib.ptr(depth), _lib.ptr(color), ws.data_ptr(), ws.numel(), _lib.current_stream()),
-                   None, "sn_mesh_raster_color")
-    return color, depth
+    return _raster("sn_mesh_raster_color", vertices, triangles, mv, fx, fy, cx, cy, height, width, znear, zfar, cull_back_faces,
+                   True if with_depth else None, vertex_colors, _shade_opts(base_color, ambient, background, gamma))
 
 
 ACCEL_LEAF_MAX = 4   # SN_RAYS_LEAF_MAX of csrc/sn_mesh_rays.h
@@ -616,6 +602,39 @@ def build_accel(vertices: np.ndarray, triangles: np.ndarray) -> np.ndarray:
     return np.concatenate([header.view(np.uint8), nodes.reshape(-1).view(np.uint8), recs.reshape(-1).view(np.uint8)])
 
 
+def _cast(fn: str, origins: Tensor, directions: Tensor, forward, accel: Tensor, n_triangles, height, width, znear, zfar, cull_back_faces,
+          triangles, colors, n_vertices, shade) -> Tuple[Optional[Tensor], Tensor]:
+    """One call of the ray cast `fn` -> (color, depth), after the checks of its arguments.  `colors`: vertex colours or None, or
+    ``MeshMaterials``; with `shade` the colour image is allocated, without it color is None."""
+    lib = _lib.load()
+    dev = accel.device
+    n = int(height) * int(width)
+    if origins.numel() != 3 * n or directions.numel() != 3 * n:
+        raise ValueError(f"the ray bundle holds {origins.numel() // 3} origins and {directions.numel() // 3} directions, the camera has "
+                         f"{height} x {width} = {n} pixels")
+    with_materials = isinstance(colors, MeshMaterials)
+    if with_materials and int(colors.triangle_material.shape[0]) != int(n_triangles):
+        raise ValueError(f"the materials are those of {int(colors.triangle_material.shape[0])} triangles, the mesh has {int(n_triangles)}")
+    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+    o, d = f32(origins), f32(directions)
+    if shade is not None and not with_materials and triangles is None:
+        raise ValueError("with_color needs the triangles")
+    if colors is not None and not with_materials and (colors.dtype != torch.uint8 or tuple(colors.shape) != (int(n_vertices), 4)):
+        raise ValueError(f"vertex_colors must be [V,4] uint8 with V = {int(n_vertices)}, got {tuple(colors.shape)} {colors.dtype}")
+    opts = _lib.SnMeshRaysOpts()
+    opts.znear, opts.zfar, opts.cull_back_faces = float(znear), float(zfar), int(bool(cull_back_faces))
+    fwd = (C.c_float * 3)(*[float(x) for x in forward])
+    with torch.cuda.device(dev):
+        held = colors.struct(dev) if with_materials else None if colors is None else colors.contiguous()
+        depth = torch.empty((height, width, 1), dtype=torch.float32, device=dev)
+        color = torch.empty((height, width, 3), dtype=torch.uint8, device=dev) if shade is not None else None
+        _lib.check(getattr(lib, fn)(_lib.ptr(o), _lib.ptr(d), int(height), int(width), fwd, _lib.ptr(accel), accel.numel(), _lib.ptr(triangles),
+                                    int(n_triangles), C.byref(held) if with_materials else _lib.ptr(held), int(n_vertices), C.byref(opts),
+                                    C.byref(shade) if shade is not None else None, _lib.ptr(depth), _lib.ptr(color), _lib.current_stream()),
+                   None, fn)
+    return color, depth
+
+
 def cast_rays(origins: Tensor, directions: Tensor, forward, accel: Tensor, n_triangles: int, height: int, width: int,
               triangles: Optional[Tensor] = None, vertex_colors: Optional[Tensor] = None, n_vertices: int = 0, with_color: bool = False,
               base_color=PYRENDER_DEFAULT_BASE_COLOR, ambient=REFERENCE_AMBIENT, background=PYRENDER_BACKGROUND, gamma: bool = True,
@@ -624,35 +643,8 @@ def cast_rays(origins: Tensor, directions: Tensor, forward, accel: Tensor, n_tri
     returns), forward: the camera's viewing axis (3 host floats), accel: ``build_accel``'s blob on the GPU -> (color [H,W,3] uint8 or None,
     z-depth [H,W,1] fp32), 0 / the background where the mesh is not drawn.  with_color needs triangles [F,3] int32 on the GPU (and takes
     vertex_colors [V,4] uint8, n_vertices = V)."""
-    lib = _lib.load()
-    dev = accel.device
-    n = int(height) * int(width)
-    if origins.numel() != 3 * n or directions.numel() != 3 * n:
-        raise ValueError(f"the ray bundle holds {origins.numel() // 3} origins and {directions.numel() // 3} directions, the camera has "
-                         f"{height} x {width} = {n} pixels")
-    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-    o, d = f32(origins), f32(directions)
-    if with_color and triangles is None:
-        raise ValueError("with_color needs the triangles")
-    if vertex_colors is not None and (vertex_colors.dtype != torch.uint8 or tuple(vertex_colors.shape) != (int(n_vertices), 4)):
-        raise ValueError(f"vertex_colors must be [V,4] uint8 with V = {int(n_vertices)}, got {tuple(vertex_colors.shape)} {vertex_colors.dtype}")
-    opts = _lib.SnMeshRaysOpts()
-    opts.znear, opts.zfar, opts.cull_back_faces = float(znear), float(zfar), int(bool(cull_back_faces))
-    shade = _lib.SnMeshShadeOpts()
-    shade.base_color[:] = [float(x) for x in base_color]
-    shade.ambient[:] = [float(x) for x in ambient]
-    shade.background[:] = [float(x) for x in background]
-    shade.gamma = int(bool(gamma))
-    fwd = (C.c_float * 3)(*[float(x) for x in forward])
-    with torch.cuda.device(dev):
-        depth = torch.empty((height, width, 1), dtype=torch.float32, device=dev)
-        color = torch.empty((height, width, 3), dtype=torch.uint8, device=dev) if with_color else None
-        vc = None if vertex_colors is None else vertex_colors.contiguous()
-        _lib.check(lib.sn_mesh_cast_rays(_lib.ptr(o), _lib.ptr(d), int(height), int(width), fwd, _lib.ptr(accel), accel.numel(),
-                                         _lib.ptr(triangles), int(n_triangles), _lib.ptr(vc), int(n_vertices), C.byref(opts),
-                                         C.byref(shade) if with_color else None, _lib.ptr(depth), _lib.ptr(color), _lib.current_stream()),
-                   None, "sn_mesh_cast_rays")
-    return color, depth
+    return _cast("sn_mesh_cast_rays", origins, directions, forward, accel, n_triangles, height, width, znear, zfar, cull_back_faces, triangles,
+                 vertex_colors, n_vertices, _shade_opts(base_color, ambient, background, gamma) if with_color else None)
 
 
 def cast_rays_materials(origins: Tensor, directions: Tensor, forward, accel: Tensor, n_triangles: int, height: int, width: int,
@@ -661,29 +653,8 @@ def cast_rays_materials(origins: Tensor, directions: Tensor, forward, accel: Ten
                         cull_back_faces: bool = True) -> Tuple[Tensor, Tensor]:
     """``sn_mesh_cast_rays_materials``: ``cast_rays(with_color=True)`` with `materials` in place of the vertex colours -> (color, depth);
     the depth is bit-identical to ``cast_rays``'s."""
-    lib = _lib.load()
-    dev = accel.device
-    n = int(height) * int(width)
-    if origins.numel() != 3 * n or directions.numel() != 3 * n:
-        raise ValueError(f"the ray bundle holds {origins.numel() // 3} origins and {directions.numel() // 3} directions, the camera has "
-                         f"{height} x {width} = {n} pixels")
-    if int(materials.triangle_material.shape[0]) != int(n_triangles):
-        raise ValueError(f"the materials are those of {int(materials.triangle_material.shape[0])} triangles, the mesh has {int(n_triangles)}")
-    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-    o, d = f32(origins), f32(directions)
-    opts = _lib.SnMeshRaysOpts()
-    opts.znear, opts.zfar, opts.cull_back_faces = float(znear), float(zfar), int(bool(cull_back_faces))
-    shade = _shade_opts(base_color, ambient, background, gamma)
-    fwd = (C.c_float * 3)(*[float(x) for x in forward])
-    with torch.cuda.device(dev):
-        mats = materials.struct(dev)
-        depth = torch.empty((height, width, 1), dtype=torch.float32, device=dev)
-        color = torch.empty((height, width, 3), dtype=torch.uint8, device=dev)
-        _lib.check(lib.sn_mesh_cast_rays_materials(_lib.ptr(o), _lib.ptr(d), int(height), int(width), fwd, _lib.ptr(accel), accel.numel(), None,
-                                                   int(n_triangles), C.byref(mats), 0, C.byref(opts), C.byref(shade), _lib.ptr(depth),
-                                                   _lib.ptr(color), _lib.current_stream()),
-                   None, "sn_mesh_cast_rays_materials")
-    return color, depth
+    return _cast("sn_mesh_cast_rays_materials", origins, directions, forward, accel, n_triangles, height, width, znear, zfar, cull_back_faces,
+                 None, materials, 0, _shade_opts(base_color, ambient, background, gamma))
 
 
 class Renderer:

@@ -79,7 +79,7 @@ int hipGetLastError(void) { return 0; }
 #define MAX_KERNELS 512
 #define MAX_LAUNCHES 64
 typedef struct { const void* host; const char* name; int n_args; uint32_t size[16]; } kernel_t;
-typedef struct { const char* name; uint64_t geom[7]; size_t n; unsigned char* args; } launch_t;
+typedef struct { const char* name; uint64_t geom[7]; size_t n; unsigned char* args; unsigned char* raw; } launch_t;
 static kernel_t g_kernels[MAX_KERNELS]; static int g_nkernels;
 static launch_t g_launches[MAX_LAUNCHES]; static int g_nlaunches;
 void stub_set_kernel_args(const char* name, int n_args, const uint32_t* sizes) {
@@ -90,7 +90,7 @@ void stub_set_kernel_args(const char* name, int n_args, const uint32_t* sizes) {
         }
 }
 void stub_clear(void) {
-    for (int i = 0; i < g_nlaunches; ++i) free(g_launches[i].args);
+    for (int i = 0; i < g_nlaunches; ++i) { free(g_launches[i].args); free(g_launches[i].raw); }
     g_nlaunches = 0;
 }
 int stub_launches(void) { return g_nlaunches; }
@@ -101,20 +101,29 @@ size_t stub_launch_args(int i, void* dst, size_t cap) {
     if (n) memcpy(dst, g_launches[i].args, n);
     return g_launches[i].n;
 }
+// the same bytes as the caller passed them, no pointer replaced (a recorder that knows which words are pointers reads a struct whose
+// padding is stack garbage through this: garbage beside a 4-byte field can look like a pointer into the arena)
+size_t stub_launch_raw_args(int i, void* dst, size_t cap) {
+    const size_t n = g_launches[i].n < cap ? g_launches[i].n : cap;
+    if (n) memcpy(dst, g_launches[i].raw, n);
+    return g_launches[i].n;
+}
 int hipLaunchKernel(const void* f, dim3_t g, dim3_t b, void** a, size_t sh, void* st) {
     (void)st;
     if (g_nlaunches == MAX_LAUNCHES) return 0;   // (weight finalisation launches more; nobody reads its log)
     launch_t* L = &g_launches[g_nlaunches++];
-    *L = (launch_t){"?", {g.x, g.y, g.z, b.x, b.y, b.z, sh}, 0, NULL};
+    *L = (launch_t){"?", {g.x, g.y, g.z, b.x, b.y, b.z, sh}, 0, NULL, NULL};
     for (int i = 0; i < g_nkernels; ++i) {
         const kernel_t* k = &g_kernels[i];
         if (k->host != f) continue;
         L->name = k->name;
         for (int j = 0; j < k->n_args; ++j) L->n += (k->size[j] + 7u) & ~7u;
         L->args = (unsigned char*)calloc(L->n ? L->n : 1, 1);
+        L->raw = (unsigned char*)calloc(L->n ? L->n : 1, 1);
         size_t at = 0;
         for (int j = 0; j < k->n_args; ++j) {
             memcpy(L->args + at, a[j], k->size[j]);
+            memcpy(L->raw + at, a[j], k->size[j]);
             for (size_t w = 0; w + 8 <= k->size[j]; w += 8) {
                 uint64_t v;
                 memcpy(&v, L->args + at + w, 8);

@@ -12,12 +12,11 @@ stub does that; every buffer of the caller -- rays, outputs, workspace -- comes 
 real runtime into the process.
 
     --out FILE   write there instead (tests/test_launch_variants_host.py runs this file on the tree's own library and compares)"""
-import ctypes as C, hashlib, importlib.util, itertools, json, math, os, re, subprocess, sys, tempfile, types
+import ctypes as C, hashlib, itertools, json, math, os, sys
 import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 PARENT = "1cb37c69c0f7f29a5c4c5f51db0d6990b4f830de"
-LLVM = "/opt/rocm/lib/llvm/bin"
 FUSED = ("sn_render_main_kernel", "sn_proposal_kernel", "sn_normals_kernel")
 FRAMES = {"small": (10, 12),     # below the 2 x 2 tiles (16 x 16 pixels) of one workgroup
           "split": (60, 72)}     # 20 workgroups = the last (only) round of 768 slots at the stub's 256 CUs: cut into segment jobs
@@ -179,58 +178,9 @@ def run_call(h, c):
 if __name__ == "__main__":
     lib_path = os.path.abspath(sys.argv[1])
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(HERE, "launch_variants.json")
-    spec = importlib.util.spec_from_file_location("signerf_amd._lib", os.path.join(ROOT, "signerf_amd", "_lib.py"))
-    _lib = importlib.util.module_from_spec(spec); spec.loader.exec_module(_lib)
-    pkg = types.ModuleType("signerf_amd"); pkg._lib = _lib
-    sys.modules["signerf_amd"] = pkg; sys.modules["signerf_amd._lib"] = _lib
-    assert "torch" not in sys.modules
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import weights_cases as wc
-    tmp = tempfile.mkdtemp()
-
-
-    def kernel_arg_sizes():
-        """{kernel: [bytes of each explicit argument]} from the metadata of the library's gfx950 code object."""
-        os.symlink(lib_path, os.path.join(tmp, "lib.so"))
-        subprocess.run([LLVM + "/llvm-objdump", "--offloading", "lib.so"], cwd=tmp, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        co, = [f for f in os.listdir(tmp) if "amdgcn" in f and "gfx950" in f]
-        notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", os.path.join(tmp, co)], capture_output=True, text=True, check=True).stdout
-        out, sizes, size = {}, [], 0
-        for ln in notes.splitlines():
-            if re.match(r"^  - \.", ln):                       # the next kernel
-                sizes = []
-            m = re.match(r"^      (?:- |  )\.size:\s+(\d+)", ln)
-            if m:
-                size = int(m.group(1))
-            m = re.match(r"^      (?:- |  )\.value_kind:\s+(\S+)", ln)
-            if m and not m.group(1).startswith("hidden"):
-                sizes.append(size)
-            m = re.match(r"^    \.name:\s+(\S+)", ln)
-            if m:
-                out[m.group(1)] = sizes
-        return out
-
-
-    ARGS = kernel_arg_sizes()
-    stub_path = os.path.join(tmp, "libamdhip64.so.7")      # the soname the library asks for: loaded first, it satisfies that request
-    subprocess.run(["gcc", "-shared", "-fPIC", "-O1", os.path.join(HERE, "hip_host_stub.c"), "-Wl,-soname,libamdhip64.so.7",
-                    "-Wl,--version-script=" + os.path.join(HERE, "hip_host_stub.map"), "-o", stub_path], check=True)
-    stub = C.CDLL(stub_path, mode=C.RTLD_GLOBAL)
-    stub.stub_launch_name.restype = C.c_char_p
-    stub.stub_launch_args.restype = C.c_size_t
-    stub.stub_launch_args.argtypes = [C.c_int, C.c_void_p, C.c_size_t]
-    lib = C.CDLL(lib_path)
-    for name, (res, args) in _lib.SIGNATURES.items():
-        fn = getattr(lib, name); fn.restype = res; fn.argtypes = args
-    for name, sizes in ARGS.items():
-        stub.stub_set_kernel_args(name.encode(), len(sizes), (C.c_uint32 * len(sizes))(*sizes))
-
-
-    def dev(nbytes):
-        p = C.c_void_p(None)
-        assert stub.hipMalloc(C.byref(p), C.c_size_t(nbytes)) == 0
-        return p.value
-
+    import stub_host
+    host = stub_host.boot(lib_path)
+    _lib, wc, stub, lib, ARGS, dev = host._lib, host.wc, host.stub, host.lib, host.args, host.dev
 
     # every buffer of the caller, once, before the first handle: their arena offsets do not depend on the handles
     BUF = {k: dev(N_MAX * 12) for k in ("origins", "directions", "rgb", "normals", "pred_normals")}

@@ -6,28 +6,15 @@ with its HIP runtime calls served by hip_host_stub.c: device memory is host memo
 returns the abs-max the case's tables have (tests/weights_cases.py builds them so, bit for bit).  Every case then goes through that
 library's own sn_create, sn_upload_weights, sn_finalize_weights, sn_debug_read, sn_debug_layout and sn_effective_precision.  torch is
 not imported: it would bring the real runtime into the process."""
-import ctypes as C, hashlib, importlib.util, json, os, sys, types
+import ctypes as C, hashlib, json, os, sys
 import numpy as np
-import subprocess, tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 PARENT = "ed0fdd52dd7be26183825987e8c228b0a2eb9134"
 lib_path = sys.argv[1]
-spec = importlib.util.spec_from_file_location("signerf_amd._lib", os.path.join(ROOT, "signerf_amd", "_lib.py"))
-_lib = importlib.util.module_from_spec(spec); spec.loader.exec_module(_lib)
-pkg = types.ModuleType("signerf_amd"); pkg._lib = _lib
-sys.modules["signerf_amd"] = pkg; sys.modules["signerf_amd._lib"] = _lib
-assert "torch" not in sys.modules
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-import weights_cases as wc
-tmp = tempfile.mkdtemp()
-stub_path = os.path.join(tmp, "libamdhip64.so.7")      # the soname the library asks for: loaded first, it satisfies that request
-subprocess.run(["gcc", "-shared", "-fPIC", "-O1", os.path.join(HERE, "hip_host_stub.c"), "-Wl,-soname,libamdhip64.so.7",
-                "-Wl,--version-script=" + os.path.join(HERE, "hip_host_stub.map"), "-o", stub_path], check=True)
-stub = C.CDLL(stub_path, mode=C.RTLD_GLOBAL)
-lib = C.CDLL(lib_path)
-for name, (res, args) in _lib.SIGNATURES.items():
-    fn = getattr(lib, name); fn.restype = res; fn.argtypes = args
+import stub_host
+host = stub_host.boot(lib_path, kernel_args=False)
+_lib, wc, stub, lib = host._lib, host.wc, host.stub, host.lib
 out = {}
 for name, case in wc.cases().items():
     bits = (C.c_uint32 * 3)(*[int(np.float32(a).view(np.uint32)) for a in case.absmax])
