@@ -21,6 +21,7 @@ SN_MESH_MATERIAL_ABI_VERSION = 1   # include/signerf_hip_mesh_material.h, checke
 SN_RAY_BATCH_ABI_VERSION = 1   # include/signerf_hip_ray_batch.h, checked the same way
 SN_PNG_ABI_VERSION = 1   # include/signerf_hip_png.h, checked the same way
 SN_LOSSES_ABI_VERSION = 1   # include/signerf_hip_losses.h, checked the same way
+SN_HASHGRID_ABI_VERSION = 1   # include/signerf_hip_hashgrid.h, checked the same way
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # SIGNERF_HIP_LIB: load another build of the library (A/B experiments with tools/ab_lib.sh); the default is the in-tree build
@@ -322,6 +323,16 @@ LOSSES_SIGNATURES = {
     "sn_loss_interlevel_backward": (C.c_int, [_FP, _FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, _FP, C.c_void_p]),
 }
 
+# The companion header include/signerf_hip_hashgrid.h (the trainable hash grid): every symbol it declares (tests/test_hashgrid_host.py
+# checks them).  Not a *_SIGNATURES table: those are the entry points tests/golden/handle_free_launches.json was recorded for, from a
+# library older than this header; what these refuse is swept by tests/test_hashgrid_host.py instead.
+HASHGRID_BINDINGS = {
+    "sn_hashgrid_abi_version": (C.c_int, []),
+    "sn_hashgrid_debug_reload_env": (C.c_int, []),
+    "sn_hashgrid_forward": (C.c_int, [_FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p]),
+    "sn_hashgrid_backward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lock = threading.Lock()
 
@@ -348,7 +359,7 @@ def load() -> C.CDLL:
         for name, (res, args) in list(SIGNATURES.items()) + (list(MESH_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items())
                                          + list(MESH_RAYS_SIGNATURES.items()) + list(MESH_MATERIAL_SIGNATURES.items())
                                          + list(RAY_BATCH_SIGNATURES.items()) + list(PNG_SIGNATURES.items())
-                                         + list(LOSSES_SIGNATURES.items())):
+                                         + list(LOSSES_SIGNATURES.items()) + list(HASHGRID_BINDINGS.items())):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise SignerfHipError(f"{LIB_PATH} does not export {name}: it was built from another include/signerf_hip.h -- rebuild it "
@@ -386,6 +397,10 @@ def load() -> C.CDLL:
         if got != SN_LOSSES_ABI_VERSION:
             raise SignerfHipError(f"{LIB_PATH} reports SN_LOSSES_ABI_VERSION {got}, this binding was written for "
                                   f"{SN_LOSSES_ABI_VERSION}: rebuild the library")
+        got = lib.sn_hashgrid_abi_version()
+        if got != SN_HASHGRID_ABI_VERSION:
+            raise SignerfHipError(f"{LIB_PATH} reports SN_HASHGRID_ABI_VERSION {got}, this binding was written for "
+                                  f"{SN_HASHGRID_ABI_VERSION}: rebuild the library")
         _lib = lib
         return lib
 

@@ -1,0 +1,143 @@
+"""The trainable hash grid: nerfstudio's torch-path ``HashEncoding`` [NS-RECALL, nerfstudio 1.0.2 ``field_components/encodings.py``;
+SURVEY.md A7] as a differentiable op in HIP (include/signerf_hip_hashgrid.h, csrc/sn_hashgrid.h) on the table a ``nn.Parameter`` holds.
+
+It is the one piece of a nerfacto field that plain torch ops do badly -- every point fetches 8 L rows and the backward pass is an
+``index_add`` over 8 L N scattered rows -- and the keystone of a training step: with it ``nerfacto.MLPWithHashEncoding(...)(q)`` is a
+differentiable module, and the rest of the field (the ``nn.Linear`` stacks, the SH encoding, ``trunc_exp``, the contraction) runs as torch
+ops (DESIGN.md §4 "Trainable hash grid").
+
+Inputs are fp32 GPU tensors: another dtype raises ``TypeError``, a CPU tensor raises ``SignerfHipError`` (there is no CPU path), a
+non-contiguous tensor is made contiguous.  What gets a gradient: the table, and ``q`` when it requires one; never the scalings.  The op is
+``once_differentiable``: a second-order request (analytic-normal losses) raises instead of being silently wrong.  ``grad_table`` is summed
+with fp32 atomics, so two backward passes may differ in its last bits; the features and ``grad_q`` are bit-reproducible.  A point with a
+non-finite coordinate, or with ``|q * scaling| >= 2**30`` at any level, gives NaN features and a NaN ``grad_q`` row and adds nothing to
+the table's gradient.
+"""
+
+from __future__ import annotations
+
+import torch
+from torch import Tensor
+from torch.autograd.function import once_differentiable
+
+from . import _lib
+
+FEATURES = (1, 2, 4, 8)
+MAX_LEVELS, MAX_LOG2_T = 32, 24
+
+
+def _typed(x, name: str) -> None:
+    if not isinstance(x, Tensor):
+        raise TypeError(f"{name}: a torch.Tensor expected, got {type(x).__name__}")
+    if x.dtype != torch.float32:
+        raise TypeError(f"{name}: fp32 expected, got {x.dtype} (the hash-grid kernels take fp32 points and fp32 tables)")
+
+
+def _prep(x, name: str) -> Tensor:
+    _typed(x, name)
+    if not x.is_cuda:
+        raise _lib.SignerfHipError(f"{name} must live on the GPU (there is no CPU path)")
+    x = x.contiguous()
+    return x if x.data_ptr() % 16 == 0 else x.clone(memory_format=torch.contiguous_format)   # (a view into the middle of a storage)
+
+
+class _HashEncode(torch.autograd.Function):
+    """(q [N,3], table [L*T,F], scalings [L], log2_T) -> enc [N, L*F]."""
+
+    @staticmethod
+    def forward(ctx, q, table, scalings, log2_T):
+        N, L, F = q.shape[0], scalings.shape[0], table.shape[1]
+        ctx.save_for_backward(q, table, scalings)   # the backward pass recomputes indices and weights from q
+        ctx.log2_T = log2_T
+        with torch.cuda.device(q.device):
+            enc = torch.empty((N, L * F), dtype=torch.float32, device=q.device)
+            if N > 0:
+                _lib.check(_lib.load().sn_hashgrid_forward(_lib.ptr(q), _lib.ptr(table), _lib.ptr(scalings), N, L, log2_T, F, _lib.ptr(enc), None,
+                                                           _lib.current_stream()), None, "sn_hashgrid_forward")
+        return enc
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        q, table, scalings = ctx.saved_tensors
+        N, L, F = q.shape[0], scalings.shape[0], table.shape[1]
+        want_q, want_table = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_q or want_table):
+            return None, None, None, None
+        g = _prep(g.to(torch.float32), "grad_enc")
+        with torch.cuda.device(q.device):
+            g_table = torch.zeros_like(table) if want_table else None     # accumulated into by ONE backward call
+            g_q = torch.empty_like(q) if want_q else None
+            if N > 0:
+                _lib.check(_lib.load().sn_hashgrid_backward(_lib.ptr(q), _lib.ptr(table), _lib.ptr(scalings), _lib.ptr(g), N, L, ctx.log2_T, F,
+                                                            _lib.ptr(g_table), _lib.ptr(g_q), _lib.current_stream()), None, "sn_hashgrid_backward")
+        return g_q, g_table, None, None
+
+
+def _check(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int):
+    for x, name in ((q, "q"), (hash_table, "hash_table"), (scalings, "scalings")):   # every dtype before any device
+        _typed(x, name)
+    q, hash_table, scalings = _prep(q, "q"), _prep(hash_table, "hash_table"), _prep(scalings, "scalings").detach()
+    if q.ndim < 1 or q.shape[-1] != 3:
+        raise ValueError(f"hash_encode: q [..., 3] expected, got {tuple(q.shape)}")
+    L = scalings.numel()
+    if scalings.ndim != 1 or not 1 <= L <= MAX_LEVELS:
+        raise ValueError(f"hash_encode: scalings [L] with 1 <= L <= {MAX_LEVELS} expected, got {tuple(scalings.shape)}")
+    if not isinstance(log2_hashmap_size, int) or not 1 <= log2_hashmap_size <= MAX_LOG2_T:
+        raise ValueError(f"hash_encode: log2_hashmap_size in 1..{MAX_LOG2_T} expected, got {log2_hashmap_size!r}")
+    if hash_table.ndim != 2 or hash_table.shape[0] != L << log2_hashmap_size or hash_table.shape[1] not in FEATURES:
+        raise ValueError(f"hash_encode: hash_table [L * 2**log2_hashmap_size, F] = [{L << log2_hashmap_size}, F] with F in {FEATURES} "
+                         f"expected, got {tuple(hash_table.shape)}")
+    if hash_table.numel() >= 2**31:
+        raise ValueError(f"hash_encode: a table of {hash_table.numel()} elements: fewer than 2**31 expected (32-bit element offsets)")
+    if not (q.device == hash_table.device == scalings.device):
+        raise ValueError(f"hash_encode: q, hash_table and scalings on one device expected, got {q.device}, {hash_table.device}, {scalings.device}")
+    return q, hash_table, scalings
+
+
+def hash_encode(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int) -> Tensor:
+    """nerfstudio's ``HashEncoding.pytorch_fwd``: q [..., 3] (the field's positions in [0, 1]), hash_table [L * 2**log2_hashmap_size, F],
+    scalings [L] -> [..., L * F], level-major.  Differentiable once, in ``hash_table`` and (when it requires a gradient) in ``q``."""
+    q, hash_table, scalings = _check(q, hash_table, scalings, log2_hashmap_size)
+    lead = q.shape[:-1]
+    enc = _HashEncode.apply(q.reshape(-1, 3), hash_table, scalings, log2_hashmap_size)
+    return enc.reshape(*lead, enc.shape[-1])
+
+
+def hash_corner_indices(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int):
+    """For inspection and tests, no gradient: (enc [..., L * F], idx [..., L, 8] int32), the table row (with its level's offset) of every
+    corner in nerfstudio's order hashed_0..7."""
+    q, hash_table, scalings = _check(q, hash_table, scalings, log2_hashmap_size)
+    q, hash_table = q.detach(), hash_table.detach()
+    lead, L, F = q.shape[:-1], scalings.numel(), hash_table.shape[1]
+    N = q.numel() // 3
+    with torch.cuda.device(q.device):
+        enc = torch.empty((*lead, L * F), dtype=torch.float32, device=q.device)
+        idx = torch.empty((*lead, L, 8), dtype=torch.int32, device=q.device)
+        if N > 0:
+            _lib.check(_lib.load().sn_hashgrid_forward(_lib.ptr(q), _lib.ptr(hash_table), _lib.ptr(scalings), N, L, log2_hashmap_size, F,
+                                                       _lib.ptr(enc), _lib.ptr(idx), _lib.current_stream()), None, "sn_hashgrid_forward")
+    return enc, idx
+
+
+def hash_encode_backward(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int, grad_enc: Tensor,
+                         grad_table: Tensor = None, want_grad_q: bool = False):
+    """The backward entry point as it is, for tests and measurements: ``grad_table`` (or None) is ACCUMULATED INTO, ``grad_q`` (or None)
+    is returned.  -> (grad_table, grad_q)."""
+    q, hash_table, scalings = _check(q, hash_table, scalings, log2_hashmap_size)
+    q, hash_table, grad_enc = q.detach(), hash_table.detach(), _prep(grad_enc, "grad_enc").detach()
+    L, F = scalings.numel(), hash_table.shape[1]
+    N = q.numel() // 3
+    if grad_enc.numel() != N * L * F:
+        raise ValueError(f"hash_encode_backward: grad_enc [..., {L * F}] for {N} points expected, got {tuple(grad_enc.shape)}")
+    if grad_table is None and not want_grad_q:
+        raise ValueError("hash_encode_backward: grad_table or want_grad_q expected")
+    if grad_table is not None and (grad_table.shape != hash_table.shape or _prep(grad_table, "grad_table").data_ptr() != grad_table.data_ptr()):
+        raise ValueError("hash_encode_backward: grad_table must be a contiguous, 16-byte aligned tensor of the table's shape")
+    with torch.cuda.device(q.device):
+        grad_q = torch.empty_like(q) if want_grad_q else None
+        if N > 0:
+            _lib.check(_lib.load().sn_hashgrid_backward(_lib.ptr(q), _lib.ptr(hash_table), _lib.ptr(scalings), _lib.ptr(grad_enc), N, L,
+                                                        log2_hashmap_size, F, _lib.ptr(grad_table), _lib.ptr(grad_q), _lib.current_stream()),
+                       None, "sn_hashgrid_backward")
+    return grad_table, grad_q

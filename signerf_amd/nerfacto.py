@@ -11,6 +11,9 @@ and what ``SIGNeRFPipeline`` touches (/root/reference/signerf/signerf_pipeline.p
 
 The modules below hold the parameters under nerfstudio's torch-path state-dict names; their arithmetic lives in
 ``csrc/`` and is reached through the C ABI -- there is no PyTorch forward and no CPU fallback.
+The exception is the training-side call surface of the containers themselves: ``HashEncoding.forward`` (the HIP op of
+``signerf_amd.hashgrid``, differentiable), ``MLP.forward`` (its ``nn.Linear`` stack as torch ops) and ``MLPWithHashEncoding.forward``;
+the eval render does not go through them.
 """
 
 from __future__ import annotations
@@ -110,6 +113,24 @@ class HashEncoding(nn.Module):
         levels = torch.arange(self.num_levels)
         return torch.floor(self.min_res * growth**levels).to(torch.float32)
 
+    def get_out_dim(self) -> int:
+        return self.num_levels * self.features_per_level
+
+    def forward(self, in_tensor: Tensor) -> Tensor:
+        """nerfstudio's ``HashEncoding.forward`` (torch path): positions [..., 3] in [0, 1] -> [..., L * F], differentiable in
+        ``hash_table`` (and in the positions when they require a gradient) through the HIP kernels of ``signerf_amd.hashgrid``."""
+        if self.implementation != "torch":
+            raise NotImplementedError(f'HashEncoding.forward: implementation={self.implementation!r}: only the torch-path grid is trainable '
+                                      "here; the tiny-cuda-nn grid (its own resolutions, dense coarse levels) has no differentiable kernel")
+        from . import hashgrid
+
+        # the scalings are a function of the constructor's arguments: cached per device, NOT a buffer (the state dict stays hash_table only)
+        cache = self.__dict__.setdefault("_scalings_cache", {})
+        dev = in_tensor.device if isinstance(in_tensor, Tensor) else None
+        if dev not in cache:
+            cache[dev] = self.scalings().to(dev)
+        return hashgrid.hash_encode(in_tensor, self.hash_table, cache[dev], self.log2_hashmap_size)
+
 
 class MLP(nn.Module):
     """Parameters of nerfstudio's torch MLP: ``layers`` = nn.Linear list (A8)."""
@@ -119,6 +140,15 @@ class MLP(nn.Module):
         dims = [in_dim] + [layer_width] * (num_layers - 1) + [out_dim]
         self.layers = nn.ModuleList([nn.Linear(dims[i], dims[i + 1]) for i in range(num_layers)])
 
+    def forward(self, in_tensor: Tensor) -> Tensor:
+        """The ``nn.Linear`` stack with a ReLU between layers and no output activation (torch ops; ``oracle.nerfacto.mlp_forward``)."""
+        x = in_tensor
+        for i, layer in enumerate(self.layers):
+            x = layer(x)
+            if i < len(self.layers) - 1:
+                x = torch.relu(x)
+        return x
+
 
 class MLPWithHashEncoding(nn.Module):
     def __init__(self, num_levels, min_res, max_res, log2_hashmap_size, features_per_level, num_layers, layer_width, out_dim,
@@ -126,6 +156,9 @@ class MLPWithHashEncoding(nn.Module):
         super().__init__()
         self.encoder = HashEncoding(num_levels, min_res, max_res, log2_hashmap_size, features_per_level, implementation=implementation)
         self.mlp = MLP(num_levels * features_per_level, num_layers, layer_width, out_dim)
+
+    def forward(self, in_tensor: Tensor) -> Tensor:
+        return self.mlp(self.encoder(in_tensor))
 
 
 class Embedding(nn.Module):

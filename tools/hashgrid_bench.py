@@ -1,0 +1,130 @@
+#!/usr/bin/env python3
+"""What the trainable hash grid costs (signerf_amd/hashgrid.py over csrc/sn_hashgrid.h) beside the same encoding as plain torch ops with
+autograd (oracle.nerfacto.hash_encode in fp32) on the same GPU, in the same process.  Recorded, not gated (DESIGN.md §4 "Trainable hash grid").
+
+Shapes: the three grids of a nerfacto step at 4096 rays -- the main field (48 samples, 16 levels, T = 2^19, max_res 2048) and the two
+proposal nets (256 and 96 samples, 5 levels, T = 2^17, max_res 128 and 256).  The points are consecutive samples along rays through the
+contracted scene, in ray-major order as training produces them (the wave merge of the table gradient depends on that order; i.i.d. points
+would not show it): origins on a sphere of radius 1.2 looking at the unit ball, stratified samples in nerfacto's piecewise spacing between
+0.05 and 1000, contracted and mapped to [0, 1].
+
+Per shape, forward + backward (table gradient, zeroing it included), the median of 50 hipEvent spans after a warm-up:
+  hip_a        the plain table gradient, one atomic add per corner and feature (SN_HASHGRID_MERGE_MAX_SCALE=-1)
+  hip_shipped  the library's default
+  hip_merge_upto[k]  equal rows merged within the wave on the levels 0..k, plain above (the sweep the shipped threshold is read from)
+  torch        oracle.nerfacto.hash_encode, fp32 torch ops with autograd
+and beside them what the bytes the table gradient adds would cost at the guide's two float-atomic rates (scattered rows, contiguous).
+
+    python tools/hashgrid_bench.py [--reps 50] [--out profiles/hashgrid_bench.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+from oracle import nerfacto as onf  # noqa: E402
+from signerf_amd import _lib, hashgrid  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--rays", type=int, default=4096)
+ap.add_argument("--reps", type=int, default=50)
+ap.add_argument("--warmup", type=int, default=5)
+ap.add_argument("--no-sweep", action="store_true")
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hashgrid_bench.json"))
+a = ap.parse_args()
+dev = torch.device("cuda", 0)
+ENV = "SN_HASHGRID_MERGE_MAX_SCALE"
+SHAPES = {"main": dict(samples=48, L=16, log2_T=19, base=16, max_res=2048), "proposal_0": dict(samples=256, L=5, log2_T=17, base=16, max_res=128),
+          "proposal_1": dict(samples=96, L=5, log2_T=17, base=16, max_res=256)}
+SCATTERED_TBPS, CONTIGUOUS_TBPS = 0.08, 1.3   # float atomic adds: 64 lanes into 64 rows / 256 contiguous bytes per wave instruction
+
+
+def ray_points(R, S, seed):
+    g = torch.Generator().manual_seed(seed)
+    o = torch.nn.functional.normalize(torch.randn(R, 3, generator=g), dim=-1) * 1.2
+    look = torch.nn.functional.normalize(torch.randn(R, 3, generator=g), dim=-1) * torch.rand(R, 1, generator=g) ** (1 / 3)
+    d = torch.nn.functional.normalize(look - o, dim=-1)
+    s = (torch.arange(S)[None, :] + torch.rand(R, S, generator=g)) / S
+    t = onf.spacing_to_euclidean(s, torch.full((R, 1), 0.05), torch.full((R, 1), 1000.0))
+    q, _ = onf.normalized_positions(o[:, None, :] + d[:, None, :] * t[..., None])
+    return q.reshape(-1, 3).contiguous()
+
+
+def span(fn):
+    for _ in range(a.warmup):
+        fn()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(a.reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return {"ms_median": round(statistics.median(times), 4), "ms_min": round(min(times), 4)}
+
+
+def set_merge(value):
+    if value is None:
+        os.environ.pop(ENV, None)
+    else:
+        os.environ[ENV] = repr(float(value))
+    _lib.check(_lib.load().sn_hashgrid_debug_reload_env(), None, "sn_hashgrid_debug_reload_env")
+
+
+results = {}
+for name, sh in SHAPES.items():
+    L, log2_T = sh["L"], sh["log2_T"]
+    q = ray_points(a.rays, sh["samples"], seed=len(name)).to(dev)
+    s = onf.hash_scalings(L, sh["base"], sh["max_res"])
+    s_dev = s.to(dev)
+    table = ((torch.rand((L << log2_T, 2), generator=torch.Generator().manual_seed(1)) * 2 - 1) * 1e-3).to(dev).requires_grad_()
+    g = torch.randn(q.shape[0], L * 2, generator=torch.Generator().manual_seed(2)).to(dev)
+
+    def hip_forward():
+        with torch.no_grad():
+            hashgrid.hash_encode(q, table, s_dev, log2_T)
+
+    def hip_step():
+        table.grad = None
+        hashgrid.hash_encode(q, table, s_dev, log2_T).backward(g)
+
+    def torch_step():
+        table.grad = None
+        onf.hash_encode(q, table, s_dev, log2_T).backward(g)
+
+    added = q.shape[0] * L * 8 * 2 * 4
+    rec = {"points": q.shape[0], "levels": L, "log2_T": log2_T, "scalings": s.tolist(), "grad_table_bytes_added": added,
+           "atomic_rate_ms": {"scattered_0.08_TBps": round(added / (SCATTERED_TBPS * 1e9), 3), "contiguous_1.3_TBps": round(added / (CONTIGUOUS_TBPS * 1e9), 3)}}
+    rec["hip_forward"] = span(hip_forward)
+    set_merge(-1.0)
+    rec["hip_a"] = span(hip_step)
+    if not a.no_sweep:
+        rec["hip_merge_upto"] = []
+        for k in range(L):
+            set_merge(s[k].item())
+            rec["hip_merge_upto"].append(dict(level=k, max_scale=s[k].item(), **span(hip_step)))
+    set_merge(None)
+    rec["hip_shipped"] = span(hip_step)
+    rec["torch"] = span(torch_step)
+    rec["torch_over_hip_shipped"] = round(rec["torch"]["ms_median"] / rec["hip_shipped"]["ms_median"], 2)
+    results[name] = rec
+    print(name, json.dumps(rec), flush=True)
+    del table, q, g
+    torch.cuda.empty_cache()
+
+doc = {"tool": "tools/hashgrid_bench.py", "device": torch.cuda.get_device_name(0), "rays": a.rays, "reps": a.reps,
+       "note": "forward + backward (table gradient) per call, ms, median of hipEvent spans; `torch`: oracle.nerfacto.hash_encode as fp32 torch "
+               "ops with autograd on the same GPU in the same process; points are ray-ordered samples through the contracted scene",
+       "results": results}
+os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+with open(a.out, "w") as f:
+    json.dump(doc, f, indent=1)
+    f.write("\n")
+print("wrote", a.out)
