@@ -66,6 +66,16 @@ struct SnPosMap {
     float lo[3], len[3];  // every kernel divides by len, as SceneBox does
 };
 
+// Frustums.get_positions alone, un-fused (sn_sample_q's first step): the WORLD position the pred-normal encoding reads.  A fused
+// o + d * mid differs from it by an ulp of p, and the encoding's sin(2 pi 2^k p) turns an ulp of p into 4 pi ulp(p): measured per sample
+// (tests/test_gpu_normals_samples.py), the fused form doubled the error of pred_normals against the fp64 reference (6.7e-6 against 2.5e-6).
+SN_DEV void sn_sample_p(const float o[3], const float d[3], float start, float end, float p[3]) {
+#pragma clang fp contract(off)
+    float t = start + end;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p[c] = o[c] + (d[c] * t) / 2.0f;
+}
+
 // Frustums.get_positions + SceneContraction(inf) + (p+2)/4 + selector (A5, A6).
 // Returns q (already multiplied by the selector) and the selector.
 SN_DEV bool sn_sample_q(const float o[3], const float d[3], float start, float end, float q[3], const SnPosMap* pm = nullptr) {

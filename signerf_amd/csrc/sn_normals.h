@@ -571,8 +571,8 @@ __global__ __launch_bounds__(256, GRID ? 1 : SN_NORMALS_WAVES) void sn_normals_k
         }
         float pe[12];
         {
-            const float tm = (t0 + t1) * 0.5f;
-            const float pw[3] = {fmaf(d[0], tm, o[0]), fmaf(d[1], tm, o[1]), fmaf(d[2], tm, o[2])};
+            float pw[3];
+            sn_sample_p(o, d, t0, t1, pw);  // the reference's own positions, bit for bit: the encoding amplifies an ulp of them
             sn_position_encoding(pw, pe, p.pe_rev_scale);
         }
         __builtin_amdgcn_sched_barrier(0);
