@@ -22,6 +22,7 @@ SN_RAY_BATCH_ABI_VERSION = 1   # include/signerf_hip_ray_batch.h, checked the sa
 SN_PNG_ABI_VERSION = 1   # include/signerf_hip_png.h, checked the same way
 SN_LOSSES_ABI_VERSION = 1   # include/signerf_hip_losses.h, checked the same way
 SN_HASHGRID_ABI_VERSION = 1   # include/signerf_hip_hashgrid.h, checked the same way
+SN_SAMPLER_ABI_VERSION = 1   # include/signerf_hip_sampler.h, checked the same way
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # SIGNERF_HIP_LIB: load another build of the library (A/B experiments with tools/ab_lib.sh); the default is the in-tree build
@@ -333,6 +334,54 @@ HASHGRID_BINDINGS = {
     "sn_hashgrid_backward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p]),
 }
 
+
+
+class SnSamplerRays(_Sized):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_samples", C.c_int32),
+        ("n_rays", C.c_int64),
+        ("origins", C.c_void_p),
+        ("directions", C.c_void_p),
+        ("nears", C.c_void_p),
+        ("fars", C.c_void_p),
+        ("near_plane", C.c_float),
+        ("far_plane", C.c_float),
+        ("spacing_mode", C.c_int32),
+        ("single_jitter", C.c_int32),
+        ("rand", C.c_void_p),
+        ("seed", C.c_uint64),
+        ("offset", C.c_uint64),
+        ("spacing_bins", C.c_void_p),
+        ("euclid_bins", C.c_void_p),
+        ("deltas", C.c_void_p),
+        ("positions", C.c_void_p),
+        ("q", C.c_void_p),
+        ("selector", C.c_void_p),
+        ("rand_out", C.c_void_p),
+    ]
+
+
+class SnSamplerPdf(_Sized):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_in", C.c_int32),
+        ("spacing_bins", C.c_void_p),
+        ("weights", C.c_void_p),
+        ("u_grid", C.c_void_p),
+        ("anneal", C.c_float),
+        ("histogram_padding", C.c_float),
+    ]
+
+
+# The companion header include/signerf_hip_sampler.h (training-mode proposal sampling): every symbol it declares
+# (tests/test_sampler_host.py checks them, and sweeps what they refuse).  Not a *_SIGNATURES table, for the reason HASHGRID_BINDINGS gives.
+SAMPLER_BINDINGS = {
+    "sn_sampler_abi_version": (C.c_int, []),
+    "sn_sampler_initial": (C.c_int, [C.POINTER(SnSamplerRays), _FP, C.c_void_p]),
+    "sn_sampler_pdf": (C.c_int, [C.POINTER(SnSamplerRays), C.POINTER(SnSamplerPdf), C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lock = threading.Lock()
 
@@ -359,7 +408,8 @@ def load() -> C.CDLL:
         for name, (res, args) in list(SIGNATURES.items()) + (list(MESH_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items())
                                          + list(MESH_RAYS_SIGNATURES.items()) + list(MESH_MATERIAL_SIGNATURES.items())
                                          + list(RAY_BATCH_SIGNATURES.items()) + list(PNG_SIGNATURES.items())
-                                         + list(LOSSES_SIGNATURES.items()) + list(HASHGRID_BINDINGS.items())):
+                                         + list(LOSSES_SIGNATURES.items()) + list(HASHGRID_BINDINGS.items())
+                                         + list(SAMPLER_BINDINGS.items())):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise SignerfHipError(f"{LIB_PATH} does not export {name}: it was built from another include/signerf_hip.h -- rebuild it "
@@ -401,6 +451,10 @@ def load() -> C.CDLL:
         if got != SN_HASHGRID_ABI_VERSION:
             raise SignerfHipError(f"{LIB_PATH} reports SN_HASHGRID_ABI_VERSION {got}, this binding was written for "
                                   f"{SN_HASHGRID_ABI_VERSION}: rebuild the library")
+        got = lib.sn_sampler_abi_version()
+        if got != SN_SAMPLER_ABI_VERSION:
+            raise SignerfHipError(f"{LIB_PATH} reports SN_SAMPLER_ABI_VERSION {got}, this binding was written for "
+                                  f"{SN_SAMPLER_ABI_VERSION}: rebuild the library")
         _lib = lib
         return lib
 

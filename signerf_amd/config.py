@@ -89,6 +89,22 @@ class NerfactoModelConfig(InstantiateConfig):
     """Training: multiplier of the orientation loss; it is formed only when the outputs hold ``rendered_orientation_loss`` [NS]."""
     pred_normal_loss_mult: float = 0.001
     """Training: multiplier of the predicted-normal loss; formed only when the outputs hold ``rendered_pred_normal_loss`` [NS]."""
+    use_single_jitter: bool = True
+    """Training: one uniform number per ray instead of one per bin edge in the samplers' stratified jitter [NS]."""
+    proposal_update_every: int = 5
+    """Training: after the warm-up the proposal networks get a gradient every this many steps [NS]."""
+    proposal_warmup: int = 5000
+    """Training: steps over which the update interval grows from 1 to ``proposal_update_every`` [NS]."""
+    use_proposal_weight_anneal: bool = True
+    """Training: resample from ``pow(weights, anneal)`` with the anneal rising from 0 to 1 [NS]."""
+    proposal_weights_anneal_slope: float = 10.0
+    """Training: slope ``b`` of the anneal's bias function ``b x / ((b - 1) x + 1)`` [NS]."""
+    proposal_weights_anneal_max_num_iters: int = 1000
+    """Training: steps over which the anneal reaches 1 [NS]."""
+    training_forward: bool = False
+    """``forward`` of a model in ``train()`` mode runs ``get_training_outputs`` (training-mode sampling, the fields as differentiable
+    torch ops around the HIP hash grid, differentiable compositing) instead of the eval render.  Off by default: ``forward`` is then the
+    eval render in either mode, as before."""
     dense_levels: int = 0
     """Memory budget of the derived gather buffers the HIP library builds beside the uploaded tables (``SnFieldDesc.dense_levels``):
     0 = default (the 11 coarsest levels of the main grid get a de-hashed copy: 1.26 GB per model for nerfacto's grid, + 0.47 GB of x-paired

@@ -3,8 +3,8 @@ csrc/sn_losses.h), behind ``torch.autograd.Function`` wrappers with nerfstudio's
 ``RaySamples.get_weights``, ``RGBRenderer`` / ``AccumulationRenderer`` in training mode, ``model_components/losses.py``].
 
 Everything here runs AFTER the field has produced per-sample densities and colours; of the field itself the hash encoding is a HIP op
-(``signerf_amd.hashgrid``) and the rest torch ops; the training-mode sampling that produces ``weights_list`` / ``ray_samples_list`` is not
-part of this package (DESIGN.md §4 "Training back half").
+(``signerf_amd.hashgrid``) and the rest torch ops; the training-mode sampling that produces ``weights_list`` / ``ray_samples_list`` is
+``signerf_amd.samplers`` (DESIGN.md §4 "Training back half", "Training-mode sampling").
 
 Inputs are fp32 GPU tensors: another dtype raises ``TypeError``, a CPU tensor raises ``SignerfHipError`` (there is no CPU path), a
 non-contiguous tensor is made contiguous.  What gets a gradient:

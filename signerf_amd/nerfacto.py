@@ -13,7 +13,9 @@ The modules below hold the parameters under nerfstudio's torch-path state-dict n
 ``csrc/`` and is reached through the C ABI -- there is no PyTorch forward and no CPU fallback.
 The exception is the training-side call surface of the containers themselves: ``HashEncoding.forward`` (the HIP op of
 ``signerf_amd.hashgrid``, differentiable), ``MLP.forward`` (its ``nn.Linear`` stack as torch ops) and ``MLPWithHashEncoding.forward``;
-the eval render does not go through them.
+the eval render does not go through them.  The training forward does: ``HashMLPDensityField.get_density_training``,
+``NerfactoField.forward_training`` and ``NerfactoModel.get_training_outputs`` (training-mode sampling in HIP, ``signerf_amd.samplers``;
+the fields as torch ops on the modules' own parameters; compositing in HIP, ``signerf_amd.losses``).
 """
 
 from __future__ import annotations
@@ -289,6 +291,60 @@ class _HipField(nn.Module):
         return out
 
 
+class _TruncExp(torch.autograd.Function):
+    """nerfstudio's ``trunc_exp`` [NS-RECALL, field_components/activations.py]: exp forwards, exp(clamp(x, max=15)) backwards."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return torch.exp(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        return g * torch.exp(torch.clamp(x, max=15.0))
+
+
+_SH4 = (0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.9461746957575601, 0.31539156525251999, 0.5462742152960396,
+        0.5900435899266435, 2.890611442640554, 0.4570457994644658, 0.3731763325901154, 1.445305721320277)
+
+
+def _sh4_encoding(directions: Tensor) -> Tensor:
+    """The 16 real SH components of degree < 4 in the eval kernel's convention for the torch path: evaluated on
+    ``get_normalized_directions`` = (d + 1) / 2 (``oracle.nerfacto.direction_encoding``).  [..., 3] -> [..., 16]."""
+    d = (directions + 1.0) / 2.0
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    xx, yy, zz = x * x, y * y, z * z
+    c0, c1, c2, c3, c4, c5, c6, c7, c8, c9, c10 = _SH4
+    return torch.stack([torch.full_like(x, c0), c1 * y, c1 * z, c1 * x, c2 * x * y, c2 * y * z, c3 * zz - c4, c2 * x * z, c5 * (xx - yy),
+                        c6 * y * (3 * xx - yy), c7 * x * y * z, c8 * y * (5 * zz - 1), c9 * z * (5 * zz - 3), c8 * x * (5 * zz - 1),
+                        c10 * z * (xx - yy), c6 * x * (xx - 3 * yy)], dim=-1)
+
+
+def _training_q(owner, ray_samples):
+    """The field's normalised positions of training samples, already multiplied by the selector, and the selector [..., 1] (fp32).
+    Samples of ``signerf_amd.samplers`` carry both (the sampler kernels' ``q`` / ``selector``, the contraction case); with
+    ``disable_scene_contraction`` -- or samples from elsewhere -- they are torch ops on the frustums' positions."""
+    cfg = owner.config
+    if cfg.implementation != "torch":
+        raise NotImplementedError(f"training forward: implementation={cfg.implementation!r}: only the torch-path fields train here (the "
+                                  "tiny-cuda-nn grid has no differentiable kernel)")
+    if cfg.hidden_dim != 64 or cfg.hidden_dim_color != 64:
+        raise NotImplementedError("training forward: wide fields (hidden_dim=128) are not built for training")
+    q, sel = getattr(ray_samples, "q", None), getattr(ray_samples, "selector", None)
+    if cfg.disable_scene_contraction or q is None or sel is None:
+        pos = ray_samples.frustums.get_positions()
+        if cfg.disable_scene_contraction:
+            aabb = (owner.scene_box.aabb if owner.scene_box is not None else torch.tensor([[-1.0, -1.0, -1.0], [1.0, 1.0, 1.0]])).to(pos)
+            q = (pos - aabb[0]) / (aabb[1] - aabb[0])
+        else:
+            mag = torch.linalg.norm(pos, ord=float("inf"), dim=-1)[..., None]
+            q = (torch.where(mag < 1, pos, (2 - (1 / mag)) * (pos / mag)) + 2.0) / 4.0
+        sel = ((q > 0.0) & (q < 1.0)).all(dim=-1)
+        q = q * sel[..., None]
+    return q.detach(), sel[..., None].to(torch.float32)
+
+
 class NerfactoField(_HipField):
     """Parameters of nerfstudio's NerfactoField (A6-A9, A13-A15) + its eval-mode call surface (``_HipField``)."""
 
@@ -314,6 +370,40 @@ class NerfactoField(_HipField):
         _, rgb, _ = self._evaluate(fr.get_positions(), fr.directions, False)
         return {FieldHeadNames.RGB: rgb}
 
+    def forward_training(self, ray_samples, appearance: str = "per_camera", compute_normals: bool = False, return_geo: bool = False) -> Dict:
+        """The field as DIFFERENTIABLE torch ops on this module's own parameters, around the HIP hash grid (``mlp_base`` =
+        ``HashEncoding.forward`` + the ``nn.Linear`` stack): {DENSITY: [...,1], RGB: [...,3]}.  The arithmetic is the eval field's
+        (``oracle.nerfacto.density_field`` / ``field_rgb``): density = average_init_density trunc_exp(h_0) selector, the SH-4 direction
+        encoding on (d + 1) / 2, ``mlp_head`` and a sigmoid.  ``appearance``: "per_camera" -- the embedding row of every sample's
+        ``camera_indices``, what nerfstudio does while training -- or "mean", the table's mean (eval with the average embedding).  The HIP
+        handle is not involved: after an optimizer step ``mark_weights_dirty()`` is still needed before the next eval render."""
+        if compute_normals:
+            raise NotImplementedError("forward_training: per-sample normals (analytic or predicted) are not built for training; a "
+                                      "predict_normals=True model trains without its normals outputs")
+        if appearance not in ("per_camera", "mean"):
+            raise ValueError(f'appearance={appearance!r}: "per_camera" or "mean" expected')
+        owner = self._owner()
+        cfg = owner.config
+        q, sel = _training_q(owner, ray_samples)
+        lead = q.shape[:-1]
+        h = self.mlp_base(q.reshape(-1, 3))
+        density = (cfg.average_init_density * _TruncExp.apply(h[:, :1])).reshape(*lead, 1) * sel
+        geo = h[:, 1:1 + self.geo_feat_dim]
+        parts = [_sh4_encoding(ray_samples.frustums.directions.reshape(-1, 3)), geo]
+        if cfg.appearance_embed_dim > 0:
+            if appearance == "per_camera":
+                if ray_samples.camera_indices is None:
+                    raise ValueError('forward_training(appearance="per_camera"): the ray samples carry no camera_indices')
+                app = self.embedding_appearance.embedding(ray_samples.camera_indices.reshape(-1).long())
+            else:
+                app = self.embedding_appearance.mean(0)[None, :].expand(h.shape[0], -1)
+            parts.append(app)
+        rgb = torch.sigmoid(self.mlp_head(torch.cat(parts, dim=-1))).reshape(*lead, 3)
+        out = {FieldHeadNames.DENSITY: density, FieldHeadNames.RGB: rgb}
+        if return_geo:
+            out["geo"] = geo.reshape(*lead, self.geo_feat_dim)
+        return out
+
 
 class HashMLPDensityField(_HipField):
     """Parameters of a proposal network (row a9) + ``density_fn`` / ``get_density`` (``_HipField``; ``get_density`` returns
@@ -327,6 +417,15 @@ class HashMLPDensityField(_HipField):
                                       "SIGNeRF's proposal_net_args_list set use_linear=False")
         self.mlp_base = MLPWithHashEncoding(num_levels, base_res, max_res, log2_hashmap_size, features_per_level, 2, hidden_dim, 1,
                                             implementation=implementation)
+
+    def get_density_training(self, ray_samples) -> Tensor:
+        """The proposal network as DIFFERENTIABLE torch ops on this module's own parameters, around the HIP hash grid: density [...,1] =
+        average_init_density trunc_exp(mlp_base(q)) selector (``oracle.nerfacto.density_field``).  What a training-mode
+        ``ProposalNetworkSampler`` is handed as its density function."""
+        owner = self._owner()
+        q, sel = _training_q(owner, ray_samples)
+        h = self.mlp_base(q.reshape(-1, 3))
+        return (owner.config.average_init_density * _TruncExp.apply(h)).reshape(*q.shape[:-1], 1) * sel
 
 
 class LazyOutputs(dict):
@@ -399,6 +498,22 @@ def _desc_of(enc: HashEncoding, hidden_dim: int, out_dim: int) -> _lib.SnHashMlp
     for i in range(_lib.SN_MAX_LEVELS):
         d.scalings[i] = sc[i] if i < len(sc) else 0.0
     return d
+
+
+def _median_depth(weights: Tensor, ray_samples) -> Tensor:
+    """``DepthRenderer("median")`` (``oracle.nerfacto.render_depth_median``) as torch ops: weights [R,S,1] -> [R,1]."""
+    steps = (ray_samples.frustums.starts + ray_samples.frustums.ends) / 2
+    cumulative = torch.cumsum(weights[..., 0], dim=-1)
+    split = torch.full((*weights.shape[:-2], 1), 0.5, dtype=weights.dtype, device=weights.device)
+    idx = torch.clamp(torch.searchsorted(cumulative.contiguous(), split, side="left"), 0, steps.shape[-2] - 1)
+    return torch.gather(steps[..., 0], dim=-1, index=idx)
+
+
+def _expected_depth(weights: Tensor, ray_samples) -> Tensor:
+    """``DepthRenderer("expected")`` (``oracle.nerfacto.render_depth_expected``) as torch ops; the clip bounds span the bundle."""
+    steps = (ray_samples.frustums.starts + ray_samples.frustums.ends) / 2
+    depth = torch.sum(weights * steps, dim=-2) / (torch.sum(weights, -2) + 1e-10)
+    return torch.clip(depth, steps.min(), steps.max()) if steps.numel() else depth
 
 
 class NerfactoModel(nn.Module):
@@ -756,7 +871,72 @@ class NerfactoModel(nn.Module):
         return self._with_normals(ray_bundle.flatten(), 1, R, (R,), single_chunk=True)
 
     def forward(self, ray_bundle: RayBundle) -> Dict[str, Tensor]:
+        if self.training and self.config.training_forward:
+            return self.get_training_outputs(ray_bundle)
         return self.get_outputs(ray_bundle)
+
+    # -- training forward -----------------------------------------------------------------------------------------
+    def _training_sampler(self):
+        """The training-mode ``ProposalNetworkSampler`` of this model's config (signerf_amd.samplers), made on first use.  Its Philox seed
+        is 0; set ``model._training_sampler().seed`` before the first step for another stream."""
+        sampler = self.__dict__.get("_train_sampler")
+        if sampler is None:
+            from . import samplers
+
+            cfg = self.config
+            n = cfg.num_proposal_iterations
+            if n < 1:
+                raise NotImplementedError("training forward: num_proposal_iterations >= 1 expected")
+            sampler = samplers.ProposalNetworkSampler(
+                num_nerf_samples_per_ray=cfg.num_nerf_samples_per_ray, num_proposal_samples_per_ray=tuple(cfg.num_proposal_samples_per_ray[:n]),
+                num_proposal_network_iterations=n, single_jitter=cfg.use_single_jitter,
+                update_sched=samplers.update_schedule(cfg.proposal_warmup, cfg.proposal_update_every),
+                initial_sampler=cfg.proposal_initial_sampler, seed=0, near_plane=cfg.near_plane, far_plane=cfg.far_plane)
+            self.__dict__["_train_sampler"] = sampler
+        return sampler
+
+    def set_training_step(self, step: int) -> None:
+        """What nerfstudio's two training callbacks do before a step: the proposal-weight anneal
+        ``bias(clip(step / N, 0, 1), slope)``, ``bias(x, b) = b x / ((b - 1) x + 1)``, and the sampler's ``step_cb``.
+        (``get_training_callbacks`` stays empty: a trainer of this package calls this itself.)"""
+        from . import samplers
+
+        cfg = self.config
+        sampler = self._training_sampler()
+        if cfg.use_proposal_weight_anneal:
+            sampler.set_anneal(samplers.anneal_at(step, cfg.proposal_weights_anneal_slope, cfg.proposal_weights_anneal_max_num_iters))
+        sampler.step_cb(step)
+
+    def get_training_outputs(self, ray_bundle: RayBundle) -> Dict:
+        """nerfstudio's training ``NerfactoModel.get_outputs`` [NS-RECALL]: training-mode proposal sampling (HIP, signerf_amd.samplers), the
+        proposal networks and the field as differentiable torch ops around the HIP hash grid (``get_density_training`` /
+        ``forward_training``), differentiable compositing (HIP, ``losses.composite``).  Flat bundle [R, ...] ->
+        ``rgb`` [R,3], ``accumulation`` [R,1], ``depth`` (median) / ``expected_depth`` [R,1] (no gradient), ``weights_list`` and
+        ``ray_samples_list`` (last entry: the main level) and ``prop_depth_i`` [R,1].  Whatever the model's mode.  The parameters are
+        read where they live, not through the HIP handle: ``mark_weights_dirty()`` after an optimizer step, before the next eval render."""
+        from . import losses
+
+        cfg = self.config
+        bg = BACKGROUNDS[cfg.background_color]
+        if cfg.background_color == "random":
+            raise NotImplementedError('training forward: background_color="random" (a fresh colour per ray) is not built; "last_sample", '
+                                      '"black" or "white" expected')
+        b = ray_bundle.flatten()
+        ray_samples, weights_list, ray_samples_list = self._training_sampler()(b, [net.get_density_training for net in self.proposal_networks])
+        field = self.field.forward_training(ray_samples, appearance="per_camera" if b.camera_indices is not None else "mean")
+        background = "last_sample" if bg is None else torch.tensor(bg, dtype=torch.float32, device=b.origins.device)
+        weights, rgb, accumulation = losses.composite(field[FieldHeadNames.DENSITY], field[FieldHeadNames.RGB], ray_samples.deltas, background)
+        weights_list.append(weights)
+        ray_samples_list.append(ray_samples)
+        outputs = {"rgb": rgb, "accumulation": accumulation}
+        with torch.no_grad():
+            outputs["depth"] = _median_depth(weights, ray_samples)
+            outputs["expected_depth"] = _expected_depth(weights, ray_samples)
+            for i in range(cfg.num_proposal_iterations):
+                outputs[f"prop_depth_{i}"] = _median_depth(weights_list[i], ray_samples_list[i])
+        outputs["weights_list"] = weights_list
+        outputs["ray_samples_list"] = ray_samples_list
+        return outputs
 
     def _with_normals(self, b: RayBundle, H: int, W: int, shape, single_chunk: bool = False) -> Dict[str, Tensor]:
         mode = self.config.compute_normals if self.config.predict_normals else "never"
