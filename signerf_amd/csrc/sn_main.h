@@ -26,15 +26,22 @@
 // (build_main_image, build_main_image_h, pack_main_images) -- keep the two in sync.
 
 // acc[rt] (tile 0) / acc[rt] (tile 1) <- bias + W . op     (exact fp32 MFMA)
-template <int RT, int KS>
+// BIAS_LAST: the products are summed from 0 and the bias is added behind them.  With the bias as the accumulator's first value every one
+// of the KS accumulation steps rounds at the BIAS's magnitude: a density pre-activation of bias 4 + terms of order 0.1 lost 2.3 bits over 32
+// steps (rms 1.5 ulp of h0 against the 0.3 ulp of one rounding; tests/test_gpu_render_samples.py) -- and exp(h0) hands them
+// to the weight.  The density layer takes this form; the other layers' outputs pass a ReLU or a sigmoid with biases of their own size.
+template <int RT, int KS, bool BIAS_LAST = false>
 SN_DEV void sn_mlp_layer_f32(const float* __restrict__ wimg, const float* __restrict__ bimg, const float* op0,
                              const float* op1, f32x16* acc0, f32x16* acc1, int lane) {
     const int h = lane >> 5;
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
-        const f32x4* b = (const f32x4*)(bimg + (rt * 2 + h) * 16);
-        f32x4 b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
-        f32x16 v = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, b3.x, b3.y, b3.z, b3.w};
+        f32x16 v = {};
+        if (!BIAS_LAST) {
+            const f32x4* b = (const f32x4*)(bimg + (rt * 2 + h) * 16);
+            f32x4 b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
+            v = f32x16{b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, b3.x, b3.y, b3.z, b3.w};
+        }
         acc0[rt] = v;
         acc1[rt] = v;
     }
@@ -47,6 +54,17 @@ SN_DEV void sn_mlp_layer_f32(const float* __restrict__ wimg, const float* __rest
             for (int e = 0; e < 4; ++e) {
                 acc0[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], op0[4 * t4 + e], acc0[rt], 0, 0, 0);
                 acc1[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], op1[4 * t4 + e], acc1[rt], 0, 0, 0);
+            }
+        }
+    }
+    if (BIAS_LAST) {
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            const float* b = bimg + (rt * 2 + h) * 16;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                acc0[rt][r] += b[r];
+                acc1[rt][r] += b[r];
             }
         }
     }
@@ -98,7 +116,7 @@ SN_DEV void sn_main_field_f32(const float* __restrict__ lds, float* feat, const 
     __builtin_amdgcn_sched_barrier(0);
     // ---- layer 2: 64 -> 16 (rows 0..15 real; row 20 duplicates row 0 for the upper half) ----
     f32x16 g0[1], g1[1];
-    sn_mlp_layer_f32<1, 32>(lds + SnMainImg::W2, lds + SnMainImg::B2, op0, op1, g0, g1, lane);
+    sn_mlp_layer_f32<1, 32, true>(lds + SnMainImg::W2, lds + SnMainImg::B2, op0, op1, g0, g1, lane);
     h0 = upper ? g1[0][8] : g0[0][0];
     if (GEO) {
 #pragma unroll

@@ -24,15 +24,19 @@
 #include "sn_main.h"
 #include "sn_stage.h"
 
-// acc[rt] <- bias + W . op for ONE 32-sample tile (exact fp32 MFMA); RT independent accumulator chains
-template <int RT, int KS>
+// acc[rt] <- bias + W . op for ONE 32-sample tile (exact fp32 MFMA); RT independent accumulator chains.  BIAS_LAST: the bias behind
+// the products instead of in front of them (sn_mlp_layer_f32: the density layer, whose 64 accumulation steps otherwise round at the bias's size)
+template <int RT, int KS, bool BIAS_LAST = false>
 SN_DEV void sn_wide_layer(const float* __restrict__ wimg, int rt_stride_floats, const float* __restrict__ bimg, const float* op, f32x16* acc, int lane) {
     const int h = lane >> 5;
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
-        const f32x4* b = (const f32x4*)(bimg + (rt * 2 + h) * 16);
-        const f32x4 b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
-        acc[rt] = f32x16{b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, b3.x, b3.y, b3.z, b3.w};
+        acc[rt] = f32x16{};
+        if (!BIAS_LAST) {
+            const f32x4* b = (const f32x4*)(bimg + (rt * 2 + h) * 16);
+            const f32x4 b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
+            acc[rt] = f32x16{b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w, b3.x, b3.y, b3.z, b3.w};
+        }
     }
 #pragma unroll
     for (int t4 = 0; t4 < KS / 4; ++t4) {
@@ -43,6 +47,14 @@ SN_DEV void sn_wide_layer(const float* __restrict__ wimg, int rt_stride_floats, 
         for (int e = 0; e < 4; ++e)
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) acc[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[rt][e], op[4 * t4 + e], acc[rt], 0, 0, 0);
+    }
+    if (BIAS_LAST) {
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            const float* b = bimg + (rt * 2 + h) * 16;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[rt][r] += b[r];
+        }
     }
 }
 
@@ -67,7 +79,7 @@ SN_DEV void sn_wide_field_tile(const float* __restrict__ lds, const float* op_in
     // ---- layer 2: 128 -> 16 (32 padded rows) ----
     {
         f32x16 a[1];
-        sn_wide_layer<1, 64>(lds + SnWideImg::W2, 0, lds + SnWideImg::B2, op, a, lane);
+        sn_wide_layer<1, 64, true>(lds + SnWideImg::W2, 0, lds + SnWideImg::B2, op, a, lane);
         g = a[0];
     }
     __builtin_amdgcn_sched_barrier(0);

@@ -191,6 +191,35 @@ def render_rays_debug(model, ray_bundle, want=("main_fetch", "main_q", "median_i
     return out, t
 
 
+def final_bins_layout(height: int, width: int, num_nerf_samples: int, chunk_rays: int) -> dict:
+    """Where a render behind the proposal sampler keeps the main kernel's euclidean bins in its workspace (csrc/sn_frame.h sn_plan_frame:
+    the expected-depth scratch, the chunk bounds, then [tile][S + 1][lane] floats; csrc/sn_frame.h tile_geometry) -> dict(offset (bytes),
+    tiles_x, tiles_y, tile_w, tile_h).  tests/test_render_oracle_host.py holds it against the recorded frame plans."""
+    align = lambda x: (x + 255) & ~255  # noqa: E731
+    n = height * width
+    tw, th = (8, 8) if height >= 8 else (64, 1)
+    return {"offset": align(n * 4) + align(-(-n // chunk_rays) * 8), "tiles_x": -(-width // tw), "tiles_y": -(-height // th), "tile_w": tw, "tile_h": th,
+            "floats": -(-width // tw) * -(-height // th) * (num_nerf_samples + 1) * 64}
+
+
+def render_with_final_bins(model, ray_bundle):
+    """Test instrumentation: the PRODUCTION ``Model.get_outputs_for_camera_ray_bundle`` of a model with proposal nets, its workspace kept
+    (as a lazy normals launch keeps it), and the final sample bins the proposal kernel left there for the main kernel.  Returns
+    (outputs {"rgb", "depth", "accumulation", "expected_depth"} [H,W,C], bins [H*W, S+1] euclidean, on the model's device)."""
+    cfg = model.config
+    if cfg.num_proposal_iterations < 1:
+        raise _lib.SignerfHipError("render_with_final_bins: the model has no proposal nets (the uniform sampler's bins are its initial bins)")
+    H, W = ray_bundle.origins.shape[:2]
+    S = cfg.num_nerf_samples_per_ray
+    raw, state = model._render_ex(ray_bundle, H, W, False, keep_state=True)
+    torch.cuda.synchronize(model.device)
+    lay = final_bins_layout(H, W, S, cfg.eval_num_rays_per_chunk)
+    ty, tx, th, tw = lay["tiles_y"], lay["tiles_x"], lay["tile_h"], lay["tile_w"]
+    eb = state["keep"][0][lay["offset"]:lay["offset"] + lay["floats"] * 4].view(torch.float32).view(ty, tx, S + 1, th, tw)
+    bins = eb.permute(0, 3, 1, 4, 2).reshape(ty * th, tx * tw, S + 1)[:H, :W].reshape(H * W, S + 1).clone()
+    return {k: raw[k].view(H, W, -1) for k in ("rgb", "depth", "accumulation", "expected_depth")}, bins
+
+
 def debug_layout(model, which: int = -1) -> dict:
     """Layout of the derived gather buffers of one field (sn_debug_layout)."""
     lib = model._ensure_engine()
