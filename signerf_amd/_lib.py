@@ -23,6 +23,8 @@ SN_PNG_ABI_VERSION = 1   # include/signerf_hip_png.h, checked the same way
 SN_LOSSES_ABI_VERSION = 1   # include/signerf_hip_losses.h, checked the same way
 SN_HASHGRID_ABI_VERSION = 1   # include/signerf_hip_hashgrid.h, checked the same way
 SN_SAMPLER_ABI_VERSION = 1   # include/signerf_hip_sampler.h, checked the same way
+SN_MLP_ABI_VERSION = 1   # include/signerf_hip_mlp.h, checked the same way
+SN_MLP_MAX_LAYERS, SN_MLP_MAX_DIM = 4, 64
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # SIGNERF_HIP_LIB: load another build of the library (A/B experiments with tools/ab_lib.sh); the default is the in-tree build
@@ -382,6 +384,29 @@ SAMPLER_BINDINGS = {
     "sn_sampler_pdf": (C.c_int, [C.POINTER(SnSamplerRays), C.POINTER(SnSamplerPdf), C.c_void_p]),
 }
 
+
+class SnMlpDesc(_Sized):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_layers", C.c_int32),
+        ("dims", C.c_int32 * (SN_MLP_MAX_LAYERS + 1)),
+        ("reserved", C.c_int32),
+        ("weights", C.c_void_p * SN_MLP_MAX_LAYERS),
+        ("biases", C.c_void_p * SN_MLP_MAX_LAYERS),
+        ("grad_weights", C.c_void_p * SN_MLP_MAX_LAYERS),
+        ("grad_biases", C.c_void_p * SN_MLP_MAX_LAYERS),
+    ]
+
+
+# The companion header include/signerf_hip_mlp.h (the trainable MLP): every symbol it declares (tests/test_mlp_host.py checks them, and
+# sweeps what they refuse).  Not a *_SIGNATURES table, for the reason HASHGRID_BINDINGS gives.
+MLP_BINDINGS = {
+    "sn_mlp_abi_version": (C.c_int, []),
+    "sn_mlp_forward": (C.c_int, [C.POINTER(SnMlpDesc), _FP, C.c_int64, _FP, C.c_void_p]),
+    "sn_mlp_backward_workspace_bytes": (C.c_size_t, [C.POINTER(SnMlpDesc), C.c_int64]),
+    "sn_mlp_backward": (C.c_int, [C.POINTER(SnMlpDesc), _FP, _FP, C.c_int64, _FP, C.c_void_p, C.c_size_t, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lock = threading.Lock()
 
@@ -409,7 +434,7 @@ def load() -> C.CDLL:
                                          + list(MESH_RAYS_SIGNATURES.items()) + list(MESH_MATERIAL_SIGNATURES.items())
                                          + list(RAY_BATCH_SIGNATURES.items()) + list(PNG_SIGNATURES.items())
                                          + list(LOSSES_SIGNATURES.items()) + list(HASHGRID_BINDINGS.items())
-                                         + list(SAMPLER_BINDINGS.items())):
+                                         + list(SAMPLER_BINDINGS.items()) + list(MLP_BINDINGS.items())):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise SignerfHipError(f"{LIB_PATH} does not export {name}: it was built from another include/signerf_hip.h -- rebuild it "
@@ -455,6 +480,10 @@ def load() -> C.CDLL:
         if got != SN_SAMPLER_ABI_VERSION:
             raise SignerfHipError(f"{LIB_PATH} reports SN_SAMPLER_ABI_VERSION {got}, this binding was written for "
                                   f"{SN_SAMPLER_ABI_VERSION}: rebuild the library")
+        got = lib.sn_mlp_abi_version()
+        if got != SN_MLP_ABI_VERSION:
+            raise SignerfHipError(f"{LIB_PATH} reports SN_MLP_ABI_VERSION {got}, this binding was written for "
+                                  f"{SN_MLP_ABI_VERSION}: rebuild the library")
         _lib = lib
         return lib
 

@@ -105,6 +105,11 @@ class NerfactoModelConfig(InstantiateConfig):
     """``forward`` of a model in ``train()`` mode runs ``get_training_outputs`` (training-mode sampling, the fields as differentiable
     torch ops around the HIP hash grid, differentiable compositing) instead of the eval render.  Off by default: ``forward`` is then the
     eval render in either mode, as before."""
+    training_mlp: str = "torch"
+    """How the ``nn.Linear`` stacks of the fields (``MLP.forward``: the main field's base and head, the proposal nets, the pred-normals
+    stack) run where they are called as modules, i.e. in the training forward: "torch" -- a GEMM, a bias and a ReLU per layer, as before --
+    or "hip": one fused HIP kernel per pass on the exact-fp32 matrix instruction (``signerf_amd.mlp``), which keeps no hidden activation
+    for the backward pass.  Default-width, torch-path fields only.  The eval render does not go through ``MLP.forward`` and is not affected."""
     dense_levels: int = 0
     """Memory budget of the derived gather buffers the HIP library builds beside the uploaded tables (``SnFieldDesc.dense_levels``):
     0 = default (the 11 coarsest levels of the main grid get a de-hashed copy: 1.26 GB per model for nerfacto's grid, + 0.47 GB of x-paired

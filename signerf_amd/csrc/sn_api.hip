@@ -10,6 +10,7 @@
 #include "../../include/signerf_hip_losses.h"
 #include "../../include/signerf_hip_hashgrid.h"
 #include "../../include/signerf_hip_sampler.h"
+#include "../../include/signerf_hip_mlp.h"
 
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -42,6 +43,7 @@
 #include "sn_losses.h"
 #include "sn_hashgrid.h"
 #include "sn_sampler.h"
+#include "sn_mlp.h"
 #include "sn_variant.h"
 #include "sn_weights.h"
 #include "sn_wide.h"
@@ -1415,3 +1417,4 @@ int sn_field_forward_geo(SnHandle h, int32_t which, const float* positions, cons
 #include "sn_api_losses.h"
 #include "sn_api_hashgrid.h"
 #include "sn_api_sampler.h"
+#include "sn_api_mlp.h"

@@ -31,7 +31,7 @@ import numpy as np
 import torch
 from torch import Tensor, nn
 
-from . import _lib
+from . import _lib, mlp
 from .cameras import Frustums, RaySamples, RayBundle, SceneBox  # noqa: F401
 from .config import NerfactoModelConfig, SIGNeRFModelConfig
 
@@ -41,6 +41,7 @@ PRECISIONS = {"fp32": 0, "fp16x2": 1, "fp16": 2}   # "fp16": opt-in, implementat
 BACKGROUNDS = {"last_sample": None, "black": (0.0, 0.0, 0.0), "white": (1.0, 1.0, 1.0), "random": (0.0, 0.0, 0.0)}
 # NerfactoModelConfig.proposal_initial_sampler [NS] -> SnRenderOpts.spacing_mode: UniformLinDispPiecewiseSampler (the default) or UniformSampler
 INITIAL_SAMPLERS = {"piecewise": 0, "uniform": 1}
+TRAINING_MLPS = ("torch", "hip")   # config.training_mlp
 
 
 class _RWLock:
@@ -135,15 +136,24 @@ class HashEncoding(nn.Module):
 
 
 class MLP(nn.Module):
-    """Parameters of nerfstudio's torch MLP: ``layers`` = nn.Linear list (A8)."""
+    """Parameters of nerfstudio's torch MLP: ``layers`` = nn.Linear list (A8).  ``implementation``: "torch" -- ``forward`` is the torch ops
+    below -- or "hip": the same parameters through ``mlp.fused_mlp`` (one HIP kernel per pass; GPU tensors, at most 4 layers of at most 64
+    units).  A plain attribute, not state: the state dict is the same either way."""
 
-    def __init__(self, in_dim: int, num_layers: int, layer_width: int, out_dim: int):
+    implementation = "torch"   # (class-level: a module pickled whole before the attribute existed still runs the torch ops)
+
+    def __init__(self, in_dim: int, num_layers: int, layer_width: int, out_dim: int, implementation: str = "torch"):
         super().__init__()
         dims = [in_dim] + [layer_width] * (num_layers - 1) + [out_dim]
         self.layers = nn.ModuleList([nn.Linear(dims[i], dims[i + 1]) for i in range(num_layers)])
+        self.implementation = implementation
 
     def forward(self, in_tensor: Tensor) -> Tensor:
         """The ``nn.Linear`` stack with a ReLU between layers and no output activation (torch ops; ``oracle.nerfacto.mlp_forward``)."""
+        if self.implementation == "hip":
+            return mlp.fused_mlp(in_tensor, [layer.weight for layer in self.layers], [layer.bias for layer in self.layers])
+        if self.implementation != "torch":
+            raise ValueError(f'MLP.implementation={self.implementation!r}: "torch" or "hip" expected')
         x = in_tensor
         for i, layer in enumerate(self.layers):
             x = layer(x)
@@ -568,6 +578,21 @@ class NerfactoModel(nn.Module):
         for i, net in enumerate(self.proposal_networks):
             net._bind(self, i)
         self.density_fns = [net.density_fn for net in self.proposal_networks]   # nerfstudio's NerfactoModel attribute [NS-RECALL, H]
+        if cfg.training_mlp not in TRAINING_MLPS:
+            raise ValueError(f"training_mlp={cfg.training_mlp!r}: one of {sorted(TRAINING_MLPS)} expected")
+        if cfg.training_mlp == "hip":
+            if cfg.implementation != "torch":
+                raise NotImplementedError(f'training_mlp="hip" with implementation={cfg.implementation!r}: the HIP MLP reads the nn.Linear '
+                                          "weights of the torch-path fields; a tiny-cuda-nn field has no trainable forward here")
+            stacks = [self.field.mlp_base.mlp, self.field.mlp_head] + [net.mlp_base.mlp for net in self.proposal_networks]
+            if cfg.predict_normals:
+                stacks.append(self.field.mlp_pred_normals)
+            for stack in stacks:
+                try:
+                    mlp.check_dims([stack.layers[0].in_features] + [layer.out_features for layer in stack.layers])
+                except ValueError as e:
+                    raise NotImplementedError(f'training_mlp="hip": {e}; wide fields train with training_mlp="torch"') from None
+                stack.implementation = "hip"
         self.camera_optimizer = CameraOptimizer(self.num_train_data, cfg.camera_optimizer_mode)
 
     @property
