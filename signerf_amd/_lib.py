@@ -25,6 +25,8 @@ SN_HASHGRID_ABI_VERSION = 1   # include/signerf_hip_hashgrid.h, checked the same
 SN_SAMPLER_ABI_VERSION = 1   # include/signerf_hip_sampler.h, checked the same way
 SN_MLP_ABI_VERSION = 1   # include/signerf_hip_mlp.h, checked the same way
 SN_MLP_MAX_LAYERS, SN_MLP_MAX_DIM = 4, 64
+SN_TRAIN_NORMALS_ABI_VERSION = 1   # include/signerf_hip_train_normals.h, checked the same way
+SN_NORMAL_LOSSES_ABI_VERSION = 1   # include/signerf_hip_normal_losses.h, checked the same way
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # SIGNERF_HIP_LIB: load another build of the library (A/B experiments with tools/ab_lib.sh); the default is the in-tree build
@@ -407,6 +409,21 @@ MLP_BINDINGS = {
     "sn_mlp_backward": (C.c_int, [C.POINTER(SnMlpDesc), _FP, _FP, C.c_int64, _FP, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
+# The companion header include/signerf_hip_train_normals.h (analytic normals of training samples): every symbol it declares
+# (tests/test_train_normals_host.py checks them).  Not a *_SIGNATURES table, for the reason HASHGRID_BINDINGS gives.
+TRAIN_NORMALS_BINDINGS = {
+    "sn_train_normals_abi_version": (C.c_int, []),
+    "sn_train_normals_analytic": (C.c_int, [_FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SnMlpDesc), _FP, _FP, C.c_void_p]),
+}
+
+# The companion header include/signerf_hip_normal_losses.h (the per-ray normal terms of a training step): every symbol it declares
+# (tests/test_train_normals_host.py checks them).  Not a *_SIGNATURES table, for the same reason.
+NORMAL_LOSSES_BINDINGS = {
+    "sn_normal_losses_abi_version": (C.c_int, []),
+    "sn_loss_normals_forward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, _FP, _FP, _FP, _FP, C.c_void_p]),
+    "sn_loss_normals_backward": (C.c_int, [_FP, _FP, _FP, C.c_int64, C.c_int32, _FP, C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lock = threading.Lock()
 
@@ -434,7 +451,8 @@ def load() -> C.CDLL:
                                          + list(MESH_RAYS_SIGNATURES.items()) + list(MESH_MATERIAL_SIGNATURES.items())
                                          + list(RAY_BATCH_SIGNATURES.items()) + list(PNG_SIGNATURES.items())
                                          + list(LOSSES_SIGNATURES.items()) + list(HASHGRID_BINDINGS.items())
-                                         + list(SAMPLER_BINDINGS.items()) + list(MLP_BINDINGS.items())):
+                                         + list(SAMPLER_BINDINGS.items()) + list(MLP_BINDINGS.items())
+                                         + list(TRAIN_NORMALS_BINDINGS.items()) + list(NORMAL_LOSSES_BINDINGS.items())):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise SignerfHipError(f"{LIB_PATH} does not export {name}: it was built from another include/signerf_hip.h -- rebuild it "
@@ -484,6 +502,14 @@ def load() -> C.CDLL:
         if got != SN_MLP_ABI_VERSION:
             raise SignerfHipError(f"{LIB_PATH} reports SN_MLP_ABI_VERSION {got}, this binding was written for "
                                   f"{SN_MLP_ABI_VERSION}: rebuild the library")
+        got = lib.sn_train_normals_abi_version()
+        if got != SN_TRAIN_NORMALS_ABI_VERSION:
+            raise SignerfHipError(f"{LIB_PATH} reports SN_TRAIN_NORMALS_ABI_VERSION {got}, this binding was written for "
+                                  f"{SN_TRAIN_NORMALS_ABI_VERSION}: rebuild the library")
+        got = lib.sn_normal_losses_abi_version()
+        if got != SN_NORMAL_LOSSES_ABI_VERSION:
+            raise SignerfHipError(f"{LIB_PATH} reports SN_NORMAL_LOSSES_ABI_VERSION {got}, this binding was written for "
+                                  f"{SN_NORMAL_LOSSES_ABI_VERSION}: rebuild the library")
         _lib = lib
         return lib
 

@@ -110,6 +110,13 @@ class NerfactoModelConfig(InstantiateConfig):
     stack) run where they are called as modules, i.e. in the training forward: "torch" -- a GEMM, a bias and a ReLU per layer, as before --
     or "hip": one fused HIP kernel per pass on the exact-fp32 matrix instruction (``signerf_amd.mlp``), which keeps no hidden activation
     for the backward pass.  Default-width, torch-path fields only.  The eval render does not go through ``MLP.forward`` and is not affected."""
+    training_normals: bool = False
+    """The normals half of a training step (``signerf_amd.train_normals``).  ``NerfactoField.forward_training(compute_normals=True)`` then
+    returns per-sample analytic normals (HIP, no gradient: nerfstudio's ``Field.get_normals`` takes the density gradient without
+    ``create_graph``) and, on a ``predict_normals`` field, the differentiable predicted normals; ``get_training_outputs`` of a
+    ``predict_normals`` model adds ``normals``, ``pred_normals``, ``rendered_orientation_loss`` and ``rendered_pred_normal_loss``, so
+    ``get_loss_dict`` gains ``orientation_loss`` and ``pred_normal_loss``.  Off by default: the training forward is then what it was, and
+    ``forward_training(compute_normals=True)`` raises ``NotImplementedError``."""
     dense_levels: int = 0
     """Memory budget of the derived gather buffers the HIP library builds beside the uploaded tables (``SnFieldDesc.dense_levels``):
     0 = default (the 11 coarsest levels of the main grid get a de-hashed copy: 1.26 GB per model for nerfacto's grid, + 0.47 GB of x-paired

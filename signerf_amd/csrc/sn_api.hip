@@ -11,6 +11,8 @@
 #include "../../include/signerf_hip_hashgrid.h"
 #include "../../include/signerf_hip_sampler.h"
 #include "../../include/signerf_hip_mlp.h"
+#include "../../include/signerf_hip_train_normals.h"
+#include "../../include/signerf_hip_normal_losses.h"
 
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -44,6 +46,8 @@
 #include "sn_hashgrid.h"
 #include "sn_sampler.h"
 #include "sn_mlp.h"
+#include "sn_train_normals.h"
+#include "sn_normal_losses.h"
 #include "sn_variant.h"
 #include "sn_weights.h"
 #include "sn_wide.h"
@@ -1418,3 +1422,5 @@ int sn_field_forward_geo(SnHandle h, int32_t which, const float* positions, cons
 #include "sn_api_hashgrid.h"
 #include "sn_api_sampler.h"
 #include "sn_api_mlp.h"
+#include "sn_api_train_normals.h"
+#include "sn_api_normal_losses.h"

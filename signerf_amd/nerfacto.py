@@ -127,12 +127,15 @@ class HashEncoding(nn.Module):
                                       "here; the tiny-cuda-nn grid (its own resolutions, dense coarse levels) has no differentiable kernel")
         from . import hashgrid
 
-        # the scalings are a function of the constructor's arguments: cached per device, NOT a buffer (the state dict stays hash_table only)
-        cache = self.__dict__.setdefault("_scalings_cache", {})
         dev = in_tensor.device if isinstance(in_tensor, Tensor) else None
+        return hashgrid.hash_encode(in_tensor, self.hash_table, self._scalings_on(dev), self.log2_hashmap_size)
+
+    def _scalings_on(self, dev) -> Tensor:
+        """The scalings are a function of the constructor's arguments: cached per device, NOT a buffer (the state dict stays hash_table only)."""
+        cache = self.__dict__.setdefault("_scalings_cache", {})
         if dev not in cache:
             cache[dev] = self.scalings().to(dev)
-        return hashgrid.hash_encode(in_tensor, self.hash_table, cache[dev], self.log2_hashmap_size)
+        return cache[dev]
 
 
 class MLP(nn.Module):
@@ -380,20 +383,26 @@ class NerfactoField(_HipField):
         _, rgb, _ = self._evaluate(fr.get_positions(), fr.directions, False)
         return {FieldHeadNames.RGB: rgb}
 
-    def forward_training(self, ray_samples, appearance: str = "per_camera", compute_normals: bool = False, return_geo: bool = False) -> Dict:
+    def forward_training(self, ray_samples, appearance: str = "per_camera", compute_normals: bool = False, return_geo: bool = False,
+                         pred_normals: Optional[bool] = None) -> Dict:
         """The field as DIFFERENTIABLE torch ops on this module's own parameters, around the HIP hash grid (``mlp_base`` =
         ``HashEncoding.forward`` + the ``nn.Linear`` stack): {DENSITY: [...,1], RGB: [...,3]}.  The arithmetic is the eval field's
         (``oracle.nerfacto.density_field`` / ``field_rgb``): density = average_init_density trunc_exp(h_0) selector, the SH-4 direction
         encoding on (d + 1) / 2, ``mlp_head`` and a sigmoid.  ``appearance``: "per_camera" -- the embedding row of every sample's
         ``camera_indices``, what nerfstudio does while training -- or "mean", the table's mean (eval with the average embedding).  The HIP
-        handle is not involved: after an optimizer step ``mark_weights_dirty()`` is still needed before the next eval render."""
-        if compute_normals:
-            raise NotImplementedError("forward_training: per-sample normals (analytic or predicted) are not built for training; a "
-                                      "predict_normals=True model trains without its normals outputs")
-        if appearance not in ("per_camera", "mean"):
-            raise ValueError(f'appearance={appearance!r}: "per_camera" or "mean" expected')
+        handle is not involved: after an optimizer step ``mark_weights_dirty()`` is still needed before the next eval render.
+        ``compute_normals`` (``config.training_normals`` only; otherwise ``NotImplementedError``) adds NORMALS [...,3], the analytic
+        normals on the same masked ``q`` the base stack sees -- HIP, no gradient, on any field -- and PRED_NORMALS [...,3], differentiable
+        in the pred-normals stack, its head and the geo features: on a ``predict_normals`` field by default, or as ``pred_normals`` says
+        (True on a field built without ``predict_normals`` raises ``ValueError``)."""
         owner = self._owner()
         cfg = owner.config
+        if compute_normals and not cfg.training_normals:
+            raise NotImplementedError("forward_training: per-sample normals (analytic or predicted) are built for training behind "
+                                      "config.training_normals=True; without it a predict_normals=True model trains without its normals "
+                                      "outputs")
+        if appearance not in ("per_camera", "mean"):
+            raise ValueError(f'appearance={appearance!r}: "per_camera" or "mean" expected')
         q, sel = _training_q(owner, ray_samples)
         lead = q.shape[:-1]
         h = self.mlp_base(q.reshape(-1, 3))
@@ -412,7 +421,35 @@ class NerfactoField(_HipField):
         out = {FieldHeadNames.DENSITY: density, FieldHeadNames.RGB: rgb}
         if return_geo:
             out["geo"] = geo.reshape(*lead, self.geo_feat_dim)
+        if compute_normals:
+            out[FieldHeadNames.NORMALS] = self._training_analytic_normals(q)
+            if cfg.predict_normals if pred_normals is None else pred_normals:
+                out[FieldHeadNames.PRED_NORMALS] = self._training_pred_normals(ray_samples, geo).reshape(*lead, 3)
         return out
+
+    def _training_analytic_normals(self, q: Tensor) -> Tensor:
+        """``Field.get_normals`` of training samples, [..., 3], on the masked positions ``q`` the base stack sees: minus the normalised
+        gradient of the pre-activation density in ``q``, by the fused HIP kernel of ``signerf_amd.train_normals`` (measured faster than the
+        two-launch route on this shape: DESIGN.md §4 "Training-mode normals").  A constant for autograd, as in nerfstudio
+        (``torch.autograd.grad`` without ``create_graph``)."""
+        from . import train_normals
+
+        enc, layers = self.mlp_base.encoder, self.mlp_base.mlp.layers
+        return train_normals.analytic_normals(q, enc.hash_table, enc._scalings_on(q.device), enc.log2_hashmap_size,
+                                              [layer.weight for layer in layers], [layer.bias for layer in layers])
+
+    def _training_pred_normals(self, ray_samples, geo: Tensor) -> Tensor:
+        """The pred-normal branch of ``NerfactoField.get_outputs`` (``oracle.nerfacto.field_pred_normals``, torch path):
+        cat[NeRFEncoding(2 frequencies) of the WORLD positions (12), geo (15)] -> ``mlp_pred_normals`` -> Linear(64, 3) -> tanh ->
+        ``F.normalize``, [N, 3].  Differentiable in the stack, the head and ``geo``; the positions get no gradient."""
+        if not hasattr(self, "mlp_pred_normals"):
+            raise ValueError("forward_training: PRED_NORMALS asked of a field built without predict_normals")
+        pos = ray_samples.frustums.get_positions().detach().reshape(-1, 3)
+        scaled = 2.0 * np.pi * pos
+        si = (scaled[..., None] * torch.tensor([1.0, 2.0], dtype=pos.dtype, device=pos.device)).reshape(pos.shape[0], -1)
+        enc = torch.sin(torch.cat([si, si + np.pi / 2.0], dim=-1))
+        x = self.mlp_pred_normals(torch.cat([enc, geo], dim=-1))
+        return torch.nn.functional.normalize(torch.tanh(self.field_head_pred_normals.net(x)), dim=-1)
 
 
 class HashMLPDensityField(_HipField):
@@ -635,7 +672,8 @@ class NerfactoModel(nn.Module):
 
     def _sampler_losses(self, outputs, metrics_dict) -> dict:
         """The training-only terms nerfacto and SIGNeRF share: interlevel and distortion loss with the config's multipliers, and the two
-        normal losses when the outputs hold their per-ray terms (per-sample normals are not exposed, so a render of this package never does)."""
+        normal losses when the outputs hold their per-ray terms (``get_training_outputs`` of a ``predict_normals`` model under
+        ``config.training_normals``; an eval render never does)."""
         from . import losses
 
         cfg = self.config
@@ -937,7 +975,9 @@ class NerfactoModel(nn.Module):
         proposal networks and the field as differentiable torch ops around the HIP hash grid (``get_density_training`` /
         ``forward_training``), differentiable compositing (HIP, ``losses.composite``).  Flat bundle [R, ...] ->
         ``rgb`` [R,3], ``accumulation`` [R,1], ``depth`` (median) / ``expected_depth`` [R,1] (no gradient), ``weights_list`` and
-        ``ray_samples_list`` (last entry: the main level) and ``prop_depth_i`` [R,1].  Whatever the model's mode.  The parameters are
+        ``ray_samples_list`` (last entry: the main level) and ``prop_depth_i`` [R,1]; with ``config.training_normals`` on a
+        ``predict_normals`` model also ``normals`` / ``pred_normals`` [R,3] (shaded, no gradient), ``rendered_orientation_loss`` [R] (no
+        gradient) and ``rendered_pred_normal_loss`` [R] (HIP, ``signerf_amd.train_normals``).  Whatever the model's mode.  The parameters are
         read where they live, not through the HIP handle: ``mark_weights_dirty()`` after an optimizer step, before the next eval render."""
         from . import losses
 
@@ -948,12 +988,23 @@ class NerfactoModel(nn.Module):
                                       '"black" or "white" expected')
         b = ray_bundle.flatten()
         ray_samples, weights_list, ray_samples_list = self._training_sampler()(b, [net.get_density_training for net in self.proposal_networks])
-        field = self.field.forward_training(ray_samples, appearance="per_camera" if b.camera_indices is not None else "mean")
+        with_normals = cfg.training_normals and cfg.predict_normals
+        field = self.field.forward_training(ray_samples, appearance="per_camera" if b.camera_indices is not None else "mean",
+                                            compute_normals=with_normals)
         background = "last_sample" if bg is None else torch.tensor(bg, dtype=torch.float32, device=b.origins.device)
         weights, rgb, accumulation = losses.composite(field[FieldHeadNames.DENSITY], field[FieldHeadNames.RGB], ray_samples.deltas, background)
         weights_list.append(weights)
         ray_samples_list.append(ray_samples)
         outputs = {"rgb": rgb, "accumulation": accumulation}
+        if with_normals:
+            from . import train_normals
+
+            # nerfacto hands both losses the weights and the analytic normals detached; the shaded normals carry no gradient here (in
+            # nerfstudio they are differentiable in the weights, but no loss reads them)
+            orientation, pred_normal, normals, pred_normals = train_normals._normal_terms(
+                weights.detach(), field[FieldHeadNames.NORMALS], field[FieldHeadNames.PRED_NORMALS], b.directions)
+            outputs.update({"normals": normals, "pred_normals": pred_normals, "rendered_orientation_loss": orientation,
+                            "rendered_pred_normal_loss": pred_normal})
         with torch.no_grad():
             outputs["depth"] = _median_depth(weights, ray_samples)
             outputs["expected_depth"] = _expected_depth(weights, ray_samples)
