@@ -11,3 +11,5 @@ from .data import (PatchPixelSampler, PatchPixelSamplerConfig, PixelSampler, Pix
 from .intersection import intersect_with_aabb  # noqa: F401
 from .nerfacto import FieldHeadNames, NerfactoModel, SIGNeRFModel  # noqa: F401
 from .poses import circle_poses, random_sphere_poses  # noqa: F401
+from .optimizers import AdamOptimizerConfig, ExponentialDecaySchedulerConfig, HipAdam, Optimizers  # noqa: F401
+from .trainer import Trainer  # noqa: F401

@@ -27,6 +27,8 @@ SN_MLP_ABI_VERSION = 1   # include/signerf_hip_mlp.h, checked the same way
 SN_MLP_MAX_LAYERS, SN_MLP_MAX_DIM = 4, 64
 SN_TRAIN_NORMALS_ABI_VERSION = 1   # include/signerf_hip_train_normals.h, checked the same way
 SN_NORMAL_LOSSES_ABI_VERSION = 1   # include/signerf_hip_normal_losses.h, checked the same way
+SN_OPTIM_ABI_VERSION = 1   # include/signerf_hip_optim.h, checked the same way
+SN_ADAM_MAX_TENSORS = 32
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # SIGNERF_HIP_LIB: load another build of the library (A/B experiments with tools/ab_lib.sh); the default is the in-tree build
@@ -424,6 +426,54 @@ NORMAL_LOSSES_BINDINGS = {
     "sn_loss_normals_backward": (C.c_int, [_FP, _FP, _FP, C.c_int64, C.c_int32, _FP, C.c_void_p]),
 }
 
+
+
+class SnAdamTensor(_Sized):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("param", C.c_void_p),
+        ("grad", C.c_void_p),
+        ("exp_avg", C.c_void_p),
+        ("exp_avg_sq", C.c_void_p),
+        ("step", C.c_void_p),
+        ("n", C.c_int64),
+        ("group", C.c_int32),
+    ]
+
+
+class SnAdamGroup(_Sized):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("lr", C.c_float),
+        ("beta1", C.c_float),
+        ("beta2", C.c_float),
+        ("eps", C.c_float),
+        ("weight_decay", C.c_float),
+        ("max_norm", C.c_float),
+    ]
+
+
+class SnAdamRecord(C.Structure):
+    """What the head of sn_adam_step's workspace holds per tensor after the call (a diagnostic)."""
+
+    _fields_ = [
+        ("skip", C.c_uint32),
+        ("grad_multiplier", C.c_float),
+        ("step_size", C.c_float),
+        ("sqrt_bc2", C.c_float),
+        ("grad_norm", C.c_double),
+    ]
+
+
+# The companion header include/signerf_hip_optim.h (the fused Adam step): every symbol it declares (tests/test_optim_host.py checks them,
+# and sweeps what they refuse).  Not a *_SIGNATURES table, for the reason HASHGRID_BINDINGS gives.
+OPTIM_BINDINGS = {
+    "sn_optim_abi_version": (C.c_int, []),
+    "sn_adam_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "sn_adam_step": (C.c_int, [C.POINTER(SnAdamTensor), C.c_int32, C.POINTER(SnAdamGroup), C.c_int32, _FP, _FP, C.c_void_p, C.c_size_t,
+                               C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 _lock = threading.Lock()
 
@@ -452,7 +502,8 @@ def load() -> C.CDLL:
                                          + list(RAY_BATCH_SIGNATURES.items()) + list(PNG_SIGNATURES.items())
                                          + list(LOSSES_SIGNATURES.items()) + list(HASHGRID_BINDINGS.items())
                                          + list(SAMPLER_BINDINGS.items()) + list(MLP_BINDINGS.items())
-                                         + list(TRAIN_NORMALS_BINDINGS.items()) + list(NORMAL_LOSSES_BINDINGS.items())):
+                                         + list(TRAIN_NORMALS_BINDINGS.items()) + list(NORMAL_LOSSES_BINDINGS.items())
+                                         + list(OPTIM_BINDINGS.items())):
             fn = getattr(lib, name, None)
             if fn is None:
                 raise SignerfHipError(f"{LIB_PATH} does not export {name}: it was built from another include/signerf_hip.h -- rebuild it "
@@ -510,6 +561,10 @@ def load() -> C.CDLL:
         if got != SN_NORMAL_LOSSES_ABI_VERSION:
             raise SignerfHipError(f"{LIB_PATH} reports SN_NORMAL_LOSSES_ABI_VERSION {got}, this binding was written for "
                                   f"{SN_NORMAL_LOSSES_ABI_VERSION}: rebuild the library")
+        got = lib.sn_optim_abi_version()
+        if got != SN_OPTIM_ABI_VERSION:
+            raise SignerfHipError(f"{LIB_PATH} reports SN_OPTIM_ABI_VERSION {got}, this binding was written for "
+                                  f"{SN_OPTIM_ABI_VERSION}: rebuild the library")
         _lib = lib
         return lib
 

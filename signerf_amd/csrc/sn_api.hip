@@ -13,6 +13,7 @@
 #include "../../include/signerf_hip_mlp.h"
 #include "../../include/signerf_hip_train_normals.h"
 #include "../../include/signerf_hip_normal_losses.h"
+#include "../../include/signerf_hip_optim.h"
 
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -48,6 +49,7 @@
 #include "sn_mlp.h"
 #include "sn_train_normals.h"
 #include "sn_normal_losses.h"
+#include "sn_optim.h"
 #include "sn_variant.h"
 #include "sn_weights.h"
 #include "sn_wide.h"
@@ -1424,3 +1426,4 @@ int sn_field_forward_geo(SnHandle h, int32_t which, const float* positions, cons
 #include "sn_api_mlp.h"
 #include "sn_api_train_normals.h"
 #include "sn_api_normal_losses.h"
+#include "sn_api_optim.h"

@@ -19,6 +19,7 @@ from dataclasses import dataclass, field
 from typing import Any, Dict
 
 from .config import SIGNeRFModelConfig
+from .optimizers import AdamOptimizerConfig, ExponentialDecaySchedulerConfig  # noqa: F401  (the optimiser side lives there)
 
 
 @dataclass
@@ -27,18 +28,6 @@ class MethodSpecification:
 
     config: Any
     description: str = "No description provided"
-
-
-@dataclass
-class AdamOptimizerConfig:
-    lr: float = 1e-2
-    eps: float = 1e-15
-
-
-@dataclass
-class ExponentialDecaySchedulerConfig:
-    lr_final: float = 1e-4
-    max_steps: int = 200000
 
 
 @dataclass
