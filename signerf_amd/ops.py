@@ -142,7 +142,8 @@ def render_rays_debug(model, ray_bundle, want=("main_fetch", "main_q", "median_i
     """``Model.get_outputs_for_camera_ray_bundle`` through ``sn_render_rays_debug``: the production kernels instantiated with their
     DUMP flag.  Returns (outputs, dump): outputs = {"rgb","depth","accumulation","expected_depth"} [H,W,C]; dump holds
     "main_fetch" [H*W,S,16,8] int64 (uint32 words), "main_q" [H*W,S,3], "median_index" [H*W] int32, "prop_fetch_k" [H*W,N_k,5,8], "prop_q_k" [H*W,N_k,3],
-    "pdf_index_k" [H*W,M_k+1] int32 -- see the header for the record format."""
+    "pdf_index_k" [H*W,M_k+1] int32 -- see the header for the record format; with "final_bins" in `want` (a model with proposal nets)
+    also "final_bins" [H*W,S+1], read from this launch's workspace as render_with_final_bins reads the production launch's."""
     lib = model._ensure_engine()
     H, W = ray_bundle.origins.shape[:2]
     dev = model.device
@@ -183,6 +184,8 @@ def render_rays_debug(model, ray_bundle, want=("main_fetch", "main_q", "median_i
                                       _lib.current_stream())
         _lib.check(st, model._handle, "sn_render_rays_debug")
         torch.cuda.synchronize(dev)
+        if "final_bins" in want and nprop > 0:
+            t["final_bins"] = _read_final_bins(keep[0], H, W, S, cfg.eval_num_rays_per_chunk)
         del keep
     out = {"rgb": rgb.view(H, W, 3), "depth": depth.view(H, W, 1), "accumulation": acc.view(H, W, 1), "expected_depth": exp.view(H, W, 1)}
     for k in list(t):
@@ -213,11 +216,16 @@ def render_with_final_bins(model, ray_bundle):
     S = cfg.num_nerf_samples_per_ray
     raw, state = model._render_ex(ray_bundle, H, W, False, keep_state=True)
     torch.cuda.synchronize(model.device)
-    lay = final_bins_layout(H, W, S, cfg.eval_num_rays_per_chunk)
-    ty, tx, th, tw = lay["tiles_y"], lay["tiles_x"], lay["tile_h"], lay["tile_w"]
-    eb = state["keep"][0][lay["offset"]:lay["offset"] + lay["floats"] * 4].view(torch.float32).view(ty, tx, S + 1, th, tw)
-    bins = eb.permute(0, 3, 1, 4, 2).reshape(ty * th, tx * tw, S + 1)[:H, :W].reshape(H * W, S + 1).clone()
+    bins = _read_final_bins(state["keep"][0], H, W, S, cfg.eval_num_rays_per_chunk)
     return {k: raw[k].view(H, W, -1) for k in ("rgb", "depth", "accumulation", "expected_depth")}, bins
+
+
+def _read_final_bins(workspace: Tensor, H: int, W: int, S: int, chunk_rays: int) -> Tensor:
+    """The [tile][S + 1][lane] bins of a finished render's workspace (final_bins_layout) as [H*W, S+1]."""
+    lay = final_bins_layout(H, W, S, chunk_rays)
+    ty, tx, th, tw = lay["tiles_y"], lay["tiles_x"], lay["tile_h"], lay["tile_w"]
+    eb = workspace[lay["offset"]:lay["offset"] + lay["floats"] * 4].view(torch.float32).view(ty, tx, S + 1, th, tw)
+    return eb.permute(0, 3, 1, 4, 2).reshape(ty * th, tx * tw, S + 1)[:H, :W].reshape(H * W, S + 1).clone()
 
 
 def debug_layout(model, which: int = -1) -> dict:
