@@ -8,26 +8,13 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
-from typing import Optional
+from typing import NamedTuple, Optional, Tuple
 
 SN_MAX_LEVELS = 16
 SN_MAX_PROPOSALS = 2
 SN_OK, SN_ERR_INVALID, SN_ERR_HIP, SN_ERR_STATE, SN_ERR_WORKSPACE = 0, 1, 2, 3, 4
 SN_ABI_VERSION = 6   # include/signerf_hip.h "ABI evolution": load() refuses a library built with another one
-SN_MESH_ABI_VERSION = 1   # include/signerf_hip_mesh.h, checked the same way
-SN_MESH_COLOR_ABI_VERSION = 1   # include/signerf_hip_mesh_color.h, checked the same way
-SN_MESH_RAYS_ABI_VERSION = 1   # include/signerf_hip_mesh_rays.h, checked the same way
-SN_MESH_MATERIAL_ABI_VERSION = 1   # include/signerf_hip_mesh_material.h, checked the same way
-SN_RAY_BATCH_ABI_VERSION = 1   # include/signerf_hip_ray_batch.h, checked the same way
-SN_PNG_ABI_VERSION = 1   # include/signerf_hip_png.h, checked the same way
-SN_LOSSES_ABI_VERSION = 1   # include/signerf_hip_losses.h, checked the same way
-SN_HASHGRID_ABI_VERSION = 1   # include/signerf_hip_hashgrid.h, checked the same way
-SN_SAMPLER_ABI_VERSION = 1   # include/signerf_hip_sampler.h, checked the same way
-SN_MLP_ABI_VERSION = 1   # include/signerf_hip_mlp.h, checked the same way
 SN_MLP_MAX_LAYERS, SN_MLP_MAX_DIM = 4, 64
-SN_TRAIN_NORMALS_ABI_VERSION = 1   # include/signerf_hip_train_normals.h, checked the same way
-SN_NORMAL_LOSSES_ABI_VERSION = 1   # include/signerf_hip_normal_losses.h, checked the same way
-SN_OPTIM_ABI_VERSION = 1   # include/signerf_hip_optim.h, checked the same way
 SN_ADAM_MAX_TENSORS = 32
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -156,10 +143,43 @@ class SnDebugLayout(_Sized):
     ]
 
 
-# name -> (restype, argtypes).  Must list every symbol include/signerf_hip.h declares
-# (tests/test_cabi.py checks the two against each other).
+class Header(NamedTuple):
+    """One public header of the C ABI and what this binding knows of it.  REGISTRY lists them in the order load() checks them;
+    tests/test_cabi.py holds every entry against its header file, the library's exports and the version the library reports."""
+
+    key: str             # "core", "mesh", ..., "optim"
+    file: str            # the file name under include/
+    version_fn: str      # the entry point that answers the header's version
+    version_macro: str   # its macro in the header (named in load()'s error text)
+    version: int         # the value load() expects the library to report
+    functions: dict      # name -> (restype, argtypes): every symbol the header declares
+    # True for the entry points tests/golden/handle_free_launches.json was recorded for.  The headers from hashgrid on are newer than
+    # the library that recording was made from; what their entry points refuse is swept by their own host tests instead.
+    recorded: bool
+
+
+REGISTRY: Tuple[Header, ...] = ()
+
+
+def _add(key: str, version: int, recorded: bool, functions: dict) -> None:
+    global REGISTRY
+    infix = "" if key == "core" else "_" + key
+    REGISTRY += (Header(key, f"signerf_hip{infix}.h", f"sn{infix}_abi_version", f"SN{infix.upper()}_ABI_VERSION", version, functions,
+                        recorded),)
+
+
+def header(key: str) -> Header:
+    return {h.key: h for h in REGISTRY}[key]
+
+
+def functions(recorded: Optional[bool] = None) -> dict:
+    """name -> (restype, argtypes) over every header, or over the headers whose ``recorded`` flag equals the argument."""
+    return {name: sig for h in REGISTRY if recorded is None or h.recorded == recorded for name, sig in h.functions.items()}
+
+
 _FP = C.c_void_p  # device pointer
-SIGNATURES = {
+# include/signerf_hip.h: the handle, rendering and the stages around it (its host test: tests/test_cabi.py)
+_add("core", version=SN_ABI_VERSION, recorded=True, functions={
     "sn_abi_version": (C.c_int, []),
     "sn_create": (C.c_int, [C.POINTER(SnFieldDesc), C.POINTER(C.c_void_p)]),
     "sn_destroy": (C.c_int, [C.c_void_p]),
@@ -195,7 +215,7 @@ SIGNATURES = {
     "sn_mask_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "sn_aabb_mask_condition": (C.c_int, [_FP, _FP, _FP, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(SnMaskOpts), _FP, _FP,
                                          C.c_void_p, C.c_size_t, C.c_void_p]),
-}
+})
 
 
 class SnMeshRasterOpts(_Sized):
@@ -207,15 +227,15 @@ class SnMeshRasterOpts(_Sized):
     ]
 
 
-# The companion header include/signerf_hip_mesh.h ("shape" masking mode): every symbol it declares (tests/test_mesh_host.py checks them).
-MESH_SIGNATURES = {
+# include/signerf_hip_mesh.h: "shape" masking mode (its host test: tests/test_mesh_host.py)
+_add("mesh", version=1, recorded=True, functions={
     "sn_mesh_abi_version": (C.c_int, []),
     "sn_mesh_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "sn_mesh_raster_depth": (C.c_int, [_FP, C.c_int64, _FP, C.c_int64, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float,
                                        C.c_int32, C.c_int32, C.POINTER(SnMeshRasterOpts), _FP, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sn_shape_mask_condition": (C.c_int, [_FP, _FP, C.c_int32, C.c_int32, C.POINTER(SnMaskOpts), _FP, _FP, C.c_void_p, C.c_size_t,
                                           C.c_void_p]),
-}
+})
 
 
 
@@ -229,9 +249,8 @@ class SnMeshShadeOpts(_Sized):
     ]
 
 
-# The companion header include/signerf_hip_mesh_color.h (the mesh's colour image, aabb mode with combine_shape_with_depth): every symbol it
-# declares (tests/test_mesh_color_host.py checks them).
-MESH_COLOR_SIGNATURES = {
+# include/signerf_hip_mesh_color.h: the mesh's colour image, aabb mode with combine_shape_with_depth (its host test: tests/test_mesh_color_host.py)
+_add("mesh_color", version=1, recorded=True, functions={
     "sn_mesh_color_abi_version": (C.c_int, []),
     "sn_mesh_color_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "sn_mesh_raster_color": (C.c_int, [_FP, C.c_int64, _FP, _FP, C.c_int64, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_float, C.c_float,
@@ -239,7 +258,7 @@ MESH_COLOR_SIGNATURES = {
                                        C.c_size_t, C.c_void_p]),
     "sn_aabb_mask_condition_combined": (C.c_int, [_FP, _FP, _FP, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(SnMaskOpts), _FP, _FP,
                                                   _FP, _FP, C.c_void_p, C.c_size_t, C.c_void_p]),
-}
+})
 
 
 class SnMeshRaysOpts(_Sized):
@@ -251,14 +270,13 @@ class SnMeshRaysOpts(_Sized):
     ]
 
 
-# The companion header include/signerf_hip_mesh_rays.h (the mesh along the camera's own rays): every symbol it declares
-# (tests/test_mesh_rays_host.py checks them).
-MESH_RAYS_SIGNATURES = {
+# include/signerf_hip_mesh_rays.h: the mesh along the camera's own rays (its host test: tests/test_mesh_rays_host.py)
+_add("mesh_rays", version=1, recorded=True, functions={
     "sn_mesh_rays_abi_version": (C.c_int, []),
     "sn_mesh_accel_bytes": (C.c_size_t, [C.c_int64]),
     "sn_mesh_cast_rays": (C.c_int, [_FP, _FP, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_size_t, _FP, C.c_int64, _FP,
                                     C.c_int64, C.POINTER(SnMeshRaysOpts), C.POINTER(SnMeshShadeOpts), _FP, _FP, C.c_void_p]),
-}
+})
 
 
 class SnMeshMaterial(C.Structure):
@@ -288,9 +306,8 @@ class SnMeshMaterials(_Sized):
     ]
 
 
-# The companion header include/signerf_hip_mesh_material.h (the mesh's colour image shaded with its .mtl materials): every symbol it
-# declares (tests/test_mesh_material_host.py checks them).
-MESH_MATERIAL_SIGNATURES = {
+# include/signerf_hip_mesh_material.h: the mesh's colour image shaded with its .mtl materials (its host test: tests/test_mesh_material_host.py)
+_add("mesh_material", version=1, recorded=True, functions={
     "sn_mesh_material_abi_version": (C.c_int, []),
     "sn_mesh_raster_color_materials": (C.c_int, [_FP, C.c_int64, C.POINTER(SnMeshMaterials), _FP, C.c_int64, C.POINTER(C.c_float), C.c_float,
                                                  C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.POINTER(SnMeshRasterOpts),
@@ -298,29 +315,26 @@ MESH_MATERIAL_SIGNATURES = {
     "sn_mesh_cast_rays_materials": (C.c_int, [_FP, _FP, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_void_p, C.c_size_t, _FP, C.c_int64,
                                               C.POINTER(SnMeshMaterials), C.c_int64, C.POINTER(SnMeshRaysOpts), C.POINTER(SnMeshShadeOpts), _FP,
                                               _FP, C.c_void_p]),
-}
+})
 
-# The companion header include/signerf_hip_ray_batch.h (rays of many cameras in one launch): every symbol it declares
-# (tests/test_ray_batch_host.py checks them).
-RAY_BATCH_SIGNATURES = {
+# include/signerf_hip_ray_batch.h: rays of many cameras in one launch (its host test: tests/test_ray_batch_host.py)
+_add("ray_batch", version=1, recorded=True, functions={
     "sn_ray_batch_abi_version": (C.c_int, []),
     "sn_generate_ray_batch": (C.c_int, [_FP, C.c_int32, _FP, _FP, _FP, C.c_int64, _FP, _FP, _FP, _FP, C.POINTER(C.c_float), _FP, _FP, _FP,
                                         C.c_int32, C.c_int32, C.c_int32, _FP, C.c_void_p]),
-}
+})
 
-# The companion header include/signerf_hip_png.h (a device uint8 image to the bytes of its .png file): every symbol it declares
-# (tests/test_png_codes_host.py checks them).
-PNG_SIGNATURES = {
+# include/signerf_hip_png.h: a device uint8 image to the bytes of its .png file (its host test: tests/test_png_codes_host.py)
+_add("png", version=1, recorded=True, functions={
     "sn_png_abi_version": (C.c_int, []),
     "sn_png_segment_bytes": (C.c_size_t, []),
     "sn_png_max_file_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "sn_png_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "sn_png_encode": (C.c_int, [_FP, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, _FP, C.c_size_t, _FP, C.c_void_p]),
-}
+})
 
-# The companion header include/signerf_hip_losses.h (differentiable compositing and the sampler losses): every symbol it declares
-# (tests/test_losses_host.py checks them).
-LOSSES_SIGNATURES = {
+# include/signerf_hip_losses.h: differentiable compositing and the sampler losses (its host test: tests/test_losses_host.py)
+_add("losses", version=1, recorded=True, functions={
     "sn_losses_abi_version": (C.c_int, []),
     "sn_loss_composite_forward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, _FP, _FP, _FP, C.c_void_p]),
     "sn_loss_composite_backward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, _FP, _FP, _FP, _FP, _FP, C.c_void_p]),
@@ -328,17 +342,15 @@ LOSSES_SIGNATURES = {
     "sn_loss_distortion_backward": (C.c_int, [_FP, _FP, _FP, C.c_int64, C.c_int32, _FP, C.c_void_p]),
     "sn_loss_interlevel_forward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p]),
     "sn_loss_interlevel_backward": (C.c_int, [_FP, _FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, _FP, C.c_void_p]),
-}
+})
 
-# The companion header include/signerf_hip_hashgrid.h (the trainable hash grid): every symbol it declares (tests/test_hashgrid_host.py
-# checks them).  Not a *_SIGNATURES table: those are the entry points tests/golden/handle_free_launches.json was recorded for, from a
-# library older than this header; what these refuse is swept by tests/test_hashgrid_host.py instead.
-HASHGRID_BINDINGS = {
+# include/signerf_hip_hashgrid.h: the trainable hash grid (its host test: tests/test_hashgrid_host.py)
+_add("hashgrid", version=1, recorded=False, functions={
     "sn_hashgrid_abi_version": (C.c_int, []),
     "sn_hashgrid_debug_reload_env": (C.c_int, []),
     "sn_hashgrid_forward": (C.c_int, [_FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p]),
     "sn_hashgrid_backward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p]),
-}
+})
 
 
 
@@ -380,13 +392,12 @@ class SnSamplerPdf(_Sized):
     ]
 
 
-# The companion header include/signerf_hip_sampler.h (training-mode proposal sampling): every symbol it declares
-# (tests/test_sampler_host.py checks them, and sweeps what they refuse).  Not a *_SIGNATURES table, for the reason HASHGRID_BINDINGS gives.
-SAMPLER_BINDINGS = {
+# include/signerf_hip_sampler.h: training-mode proposal sampling (its host test: tests/test_sampler_host.py)
+_add("sampler", version=1, recorded=False, functions={
     "sn_sampler_abi_version": (C.c_int, []),
     "sn_sampler_initial": (C.c_int, [C.POINTER(SnSamplerRays), _FP, C.c_void_p]),
     "sn_sampler_pdf": (C.c_int, [C.POINTER(SnSamplerRays), C.POINTER(SnSamplerPdf), C.c_void_p]),
-}
+})
 
 
 class SnMlpDesc(_Sized):
@@ -402,29 +413,26 @@ class SnMlpDesc(_Sized):
     ]
 
 
-# The companion header include/signerf_hip_mlp.h (the trainable MLP): every symbol it declares (tests/test_mlp_host.py checks them, and
-# sweeps what they refuse).  Not a *_SIGNATURES table, for the reason HASHGRID_BINDINGS gives.
-MLP_BINDINGS = {
+# include/signerf_hip_mlp.h: the trainable MLP (its host test: tests/test_mlp_host.py)
+_add("mlp", version=1, recorded=False, functions={
     "sn_mlp_abi_version": (C.c_int, []),
     "sn_mlp_forward": (C.c_int, [C.POINTER(SnMlpDesc), _FP, C.c_int64, _FP, C.c_void_p]),
     "sn_mlp_backward_workspace_bytes": (C.c_size_t, [C.POINTER(SnMlpDesc), C.c_int64]),
     "sn_mlp_backward": (C.c_int, [C.POINTER(SnMlpDesc), _FP, _FP, C.c_int64, _FP, C.c_void_p, C.c_size_t, C.c_void_p]),
-}
+})
 
-# The companion header include/signerf_hip_train_normals.h (analytic normals of training samples): every symbol it declares
-# (tests/test_train_normals_host.py checks them).  Not a *_SIGNATURES table, for the reason HASHGRID_BINDINGS gives.
-TRAIN_NORMALS_BINDINGS = {
+# include/signerf_hip_train_normals.h: analytic normals of training samples (its host test: tests/test_train_normals_host.py)
+_add("train_normals", version=1, recorded=False, functions={
     "sn_train_normals_abi_version": (C.c_int, []),
     "sn_train_normals_analytic": (C.c_int, [_FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SnMlpDesc), _FP, _FP, C.c_void_p]),
-}
+})
 
-# The companion header include/signerf_hip_normal_losses.h (the per-ray normal terms of a training step): every symbol it declares
-# (tests/test_train_normals_host.py checks them).  Not a *_SIGNATURES table, for the same reason.
-NORMAL_LOSSES_BINDINGS = {
+# include/signerf_hip_normal_losses.h: the per-ray normal terms of a training step (its host test: tests/test_train_normals_host.py)
+_add("normal_losses", version=1, recorded=False, functions={
     "sn_normal_losses_abi_version": (C.c_int, []),
     "sn_loss_normals_forward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, _FP, _FP, _FP, _FP, C.c_void_p]),
     "sn_loss_normals_backward": (C.c_int, [_FP, _FP, _FP, C.c_int64, C.c_int32, _FP, C.c_void_p]),
-}
+})
 
 
 
@@ -465,14 +473,13 @@ class SnAdamRecord(C.Structure):
     ]
 
 
-# The companion header include/signerf_hip_optim.h (the fused Adam step): every symbol it declares (tests/test_optim_host.py checks them,
-# and sweeps what they refuse).  Not a *_SIGNATURES table, for the reason HASHGRID_BINDINGS gives.
-OPTIM_BINDINGS = {
+# include/signerf_hip_optim.h: the fused Adam step (its host test: tests/test_optim_host.py)
+_add("optim", version=1, recorded=False, functions={
     "sn_optim_abi_version": (C.c_int, []),
     "sn_adam_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int64]),
     "sn_adam_step": (C.c_int, [C.POINTER(SnAdamTensor), C.c_int32, C.POINTER(SnAdamGroup), C.c_int32, _FP, _FP, C.c_void_p, C.c_size_t,
                                C.c_void_p]),
-}
+})
 
 _lib: Optional[C.CDLL] = None
 _lock = threading.Lock()
@@ -497,74 +504,18 @@ def load() -> C.CDLL:
             lib = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover
             raise SignerfHipError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in list(SIGNATURES.items()) + (list(MESH_SIGNATURES.items()) + list(MESH_COLOR_SIGNATURES.items())
-                                         + list(MESH_RAYS_SIGNATURES.items()) + list(MESH_MATERIAL_SIGNATURES.items())
-                                         + list(RAY_BATCH_SIGNATURES.items()) + list(PNG_SIGNATURES.items())
-                                         + list(LOSSES_SIGNATURES.items()) + list(HASHGRID_BINDINGS.items())
-                                         + list(SAMPLER_BINDINGS.items()) + list(MLP_BINDINGS.items())
-                                         + list(TRAIN_NORMALS_BINDINGS.items()) + list(NORMAL_LOSSES_BINDINGS.items())
-                                         + list(OPTIM_BINDINGS.items())):
+        for name, (res, args) in functions().items():
             fn = getattr(lib, name, None)
             if fn is None:
                 raise SignerfHipError(f"{LIB_PATH} does not export {name}: it was built from another include/signerf_hip.h -- rebuild it "
                                       "(`python -m signerf_amd.build --force`)")
             fn.restype = res
             fn.argtypes = args
-        got = lib.sn_abi_version()
-        if got != SN_ABI_VERSION:
-            raise SignerfHipError(f"{LIB_PATH} reports SN_ABI_VERSION {got}, this binding was written for {SN_ABI_VERSION}: rebuild the library")
-        got = lib.sn_mesh_abi_version()
-        if got != SN_MESH_ABI_VERSION:
-            raise SignerfHipError(f"{LIB_PATH} reports SN_MESH_ABI_VERSION {got}, this binding was written for {SN_MESH_ABI_VERSION}: "
-                                  "rebuild the library")
-        got = lib.sn_mesh_color_abi_version()
-        if got != SN_MESH_COLOR_ABI_VERSION:
-            raise SignerfHipError(f"{LIB_PATH} reports SN_MESH_COLOR_ABI_VERSION {got}, this binding was written for "
-                                  f"{SN_MESH_COLOR_ABI_VERSION}: rebuild the library")
-        got = lib.sn_mesh_rays_abi_version()
-        if got != SN_MESH_RAYS_ABI_VERSION:
-            raise SignerfHipError(f"{LIB_PATH} reports SN_MESH_RAYS_ABI_VERSION {got}, this binding was written for "
-                                  f"{SN_MESH_RAYS_ABI_VERSION}: rebuild the library")
-        got = lib.sn_mesh_material_abi_version()
-        if got != SN_MESH_MATERIAL_ABI_VERSION:
-            raise SignerfHipError(f"{LIB_PATH} reports SN_MESH_MATERIAL_ABI_VERSION {got}, this binding was written for "
-                                  f"{SN_MESH_MATERIAL_ABI_VERSION}: rebuild the library")
-        got = lib.sn_ray_batch_abi_version()
-        if got != SN_RAY_BATCH_ABI_VERSION:
-            raise SignerfHipError(f"{LIB_PATH} reports SN_RAY_BATCH_ABI_VERSION {got}, this binding was written for "
-                                  f"{SN_RAY_BATCH_ABI_VERSION}: rebuild the library")
-        got = lib.sn_png_abi_version()
-        if got != SN_PNG_ABI_VERSION:
-            raise SignerfHipError(f"{LIB_PATH} reports SN_PNG_ABI_VERSION {got}, this binding was written for "
-                                  f"{SN_PNG_ABI_VERSION}: rebuild the library")
-        got = lib.sn_losses_abi_version()
-        if got != SN_LOSSES_ABI_VERSION:
-            raise SignerfHipError(f"{LIB_PATH} reports SN_LOSSES_ABI_VERSION {got}, this binding was written for "
-                                  f"{SN_LOSSES_ABI_VERSION}: rebuild the library")
-        got = lib.sn_hashgrid_abi_version()
-        if got != SN_HASHGRID_ABI_VERSION:
-            raise SignerfHipError(f"{LIB_PATH} reports SN_HASHGRID_ABI_VERSION {got}, this binding was written for "
-                                  f"{SN_HASHGRID_ABI_VERSION}: rebuild the library")
-        got = lib.sn_sampler_abi_version()
-        if got != SN_SAMPLER_ABI_VERSION:
-            raise SignerfHipError(f"{LIB_PATH} reports SN_SAMPLER_ABI_VERSION {got}, this binding was written for "
-                                  f"{SN_SAMPLER_ABI_VERSION}: rebuild the library")
-        got = lib.sn_mlp_abi_version()
-        if got != SN_MLP_ABI_VERSION:
-            raise SignerfHipError(f"{LIB_PATH} reports SN_MLP_ABI_VERSION {got}, this binding was written for "
-                                  f"{SN_MLP_ABI_VERSION}: rebuild the library")
-        got = lib.sn_train_normals_abi_version()
-        if got != SN_TRAIN_NORMALS_ABI_VERSION:
-            raise SignerfHipError(f"{LIB_PATH} reports SN_TRAIN_NORMALS_ABI_VERSION {got}, this binding was written for "
-                                  f"{SN_TRAIN_NORMALS_ABI_VERSION}: rebuild the library")
-        got = lib.sn_normal_losses_abi_version()
-        if got != SN_NORMAL_LOSSES_ABI_VERSION:
-            raise SignerfHipError(f"{LIB_PATH} reports SN_NORMAL_LOSSES_ABI_VERSION {got}, this binding was written for "
-                                  f"{SN_NORMAL_LOSSES_ABI_VERSION}: rebuild the library")
-        got = lib.sn_optim_abi_version()
-        if got != SN_OPTIM_ABI_VERSION:
-            raise SignerfHipError(f"{LIB_PATH} reports SN_OPTIM_ABI_VERSION {got}, this binding was written for "
-                                  f"{SN_OPTIM_ABI_VERSION}: rebuild the library")
+        for h in REGISTRY:
+            got = getattr(lib, h.version_fn)()
+            if got != h.version:
+                raise SignerfHipError(f"{LIB_PATH} reports {h.version_macro} {got}, this binding was written for {h.version}: "
+                                      "rebuild the library")
         _lib = lib
         return lib
 
@@ -585,6 +536,24 @@ def ptr(t) -> Optional[int]:
     if not t.is_contiguous():
         raise SignerfHipError("tensor must be contiguous")
     return t.data_ptr()
+
+
+def typed(x, name: str, takes: str) -> None:
+    """Raises TypeError unless ``x`` is an fp32 tensor; ``takes`` is the calling module's remark on what its kernels take."""
+    import torch
+
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name}: a torch.Tensor expected, got {type(x).__name__}")
+    if x.dtype != torch.float32:
+        raise TypeError(f"{name}: fp32 expected, got {x.dtype} ({takes})")
+
+
+def prep(x, name: str, takes: str):
+    """``typed``, then the device check; returns ``x`` contiguous."""
+    typed(x, name, takes)
+    if not x.is_cuda:
+        raise SignerfHipError(f"{name} must live on the GPU (there is no CPU path)")
+    return x.contiguous()
 
 
 def current_stream() -> int:

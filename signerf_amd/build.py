@@ -14,14 +14,13 @@ import re
 import subprocess
 import sys
 
+from . import _lib   # (a plain module: the registry of public headers, no torch)
+
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libsignerf_hip.so")
 SOURCES = ["sn_api.hip"]
-HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h) for h in (
-    "signerf_hip.h", "signerf_hip_mesh.h", "signerf_hip_mesh_color.h", "signerf_hip_mesh_rays.h", "signerf_hip_mesh_material.h", "signerf_hip_ray_batch.h", "signerf_hip_png.h",
-    "signerf_hip_losses.h", "signerf_hip_hashgrid.h", "signerf_hip_sampler.h", "signerf_hip_mlp.h", "signerf_hip_train_normals.h",
-    "signerf_hip_normal_losses.h", "signerf_hip_optim.h")]
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h.file) for h in _lib.REGISTRY]
 ARCH = "gfx950"
 # Code-generation flags of the device code (tools/isa_hazard_scan.py compiles with the same ones).
 #   -fno-slp-vectorize, -disable-vector-combine: keep hipcc from packing neighbouring fp32 operations into v_pk_fma_f32 /

@@ -24,20 +24,11 @@ from . import _lib
 
 FEATURES = (1, 2, 4, 8)
 MAX_LEVELS, MAX_LOG2_T = 32, 24
-
-
-def _typed(x, name: str) -> None:
-    if not isinstance(x, Tensor):
-        raise TypeError(f"{name}: a torch.Tensor expected, got {type(x).__name__}")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{name}: fp32 expected, got {x.dtype} (the hash-grid kernels take fp32 points and fp32 tables)")
+TAKES = "the hash-grid kernels take fp32 points and fp32 tables"
 
 
 def _prep(x, name: str) -> Tensor:
-    _typed(x, name)
-    if not x.is_cuda:
-        raise _lib.SignerfHipError(f"{name} must live on the GPU (there is no CPU path)")
-    x = x.contiguous()
+    x = _lib.prep(x, name, TAKES)
     return x if x.data_ptr() % 16 == 0 else x.clone(memory_format=torch.contiguous_format)   # (a view into the middle of a storage)
 
 
@@ -76,7 +67,7 @@ class _HashEncode(torch.autograd.Function):
 
 def _check(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int):
     for x, name in ((q, "q"), (hash_table, "hash_table"), (scalings, "scalings")):   # every dtype before any device
-        _typed(x, name)
+        _lib.typed(x, name, TAKES)
     q, hash_table, scalings = _prep(q, "q"), _prep(hash_table, "hash_table"), _prep(scalings, "scalings").detach()
     if q.ndim < 1 or q.shape[-1] != 3:
         raise ValueError(f"hash_encode: q [..., 3] expected, got {tuple(q.shape)}")

@@ -27,14 +27,7 @@ from torch import Tensor
 from . import _lib
 
 
-def _prep(x, name: str) -> Tensor:
-    if not isinstance(x, Tensor):
-        raise TypeError(f"{name}: a torch.Tensor expected, got {type(x).__name__}")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{name}: fp32 expected, got {x.dtype} (the loss kernels are fp32 in, fp64 inside, fp32 out)")
-    if not x.is_cuda:
-        raise _lib.SignerfHipError(f"{name} must live on the GPU (there is no CPU path)")
-    return x.contiguous()
+TAKES = "the loss kernels are fp32 in, fp64 inside, fp32 out"
 
 
 def _grad(g: Optional[Tensor]) -> Optional[Tensor]:
@@ -154,7 +147,7 @@ def _rows(x: Tensor, last: int) -> Tensor:
 
 def get_weights(deltas: Tensor, densities: Tensor) -> Tensor:
     """``RaySamples.get_weights``: deltas, densities [..., S, 1] -> weights [..., S, 1] = nan_to_num(alpha_i T_i)."""
-    deltas, densities = _prep(deltas, "deltas"), _prep(densities, "densities")
+    deltas, densities = _lib.prep(deltas, "deltas", TAKES), _lib.prep(densities, "densities", TAKES)
     if deltas.shape != densities.shape or deltas.ndim < 2 or deltas.shape[-1] != 1:
         raise ValueError(f"get_weights: deltas and densities [..., S, 1] expected, got {tuple(deltas.shape)} and {tuple(densities.shape)}")
     _check_samples(deltas.shape[-2], "get_weights")
@@ -168,7 +161,7 @@ def composite(densities: Tensor, rgbs: Tensor, deltas: Tensor,
     colours): densities, deltas [..., S, 1], rgbs [..., S, 3] -> (weights [..., S, 1], rgb [..., 3], accumulation [..., 1]).
     ``background_color``: "last_sample" (nerfacto's default; its dependence on the last sample's colour is differentiated) or a constant
     colour, a Tensor [3]."""
-    densities, rgbs, deltas = _prep(densities, "densities"), _prep(rgbs, "rgbs"), _prep(deltas, "deltas")
+    densities, rgbs, deltas = _lib.prep(densities, "densities", TAKES), _lib.prep(rgbs, "rgbs", TAKES), _lib.prep(deltas, "deltas", TAKES)
     if deltas.shape != densities.shape or deltas.ndim < 2 or deltas.shape[-1] != 1 or rgbs.shape != (*densities.shape[:-1], 3):
         raise ValueError(f"composite: densities, deltas [..., S, 1] and rgbs [..., S, 3] expected, got {tuple(densities.shape)}, "
                          f"{tuple(deltas.shape)}, {tuple(rgbs.shape)}")
@@ -178,7 +171,7 @@ def composite(densities: Tensor, rgbs: Tensor, deltas: Tensor,
             raise ValueError(f'background_color={background_color!r}: "last_sample" or a Tensor [3] expected')
         bg = None
     else:
-        bg = _prep(background_color, "background_color").detach()
+        bg = _lib.prep(background_color, "background_color", TAKES).detach()
         if bg.shape != (3,):
             raise ValueError(f"background_color: a Tensor [3] expected, got {tuple(bg.shape)}")
     lead = densities.shape[:-2]
@@ -195,7 +188,7 @@ def ray_samples_to_sdist(ray_samples) -> Tensor:
 
 def lossfun_distortion(t: Tensor, w: Tensor) -> Tensor:
     """mip-NeRF 360's distortion loss of a step function: t [..., S+1] edges, w [..., S] weights -> [...], one value per ray."""
-    t, w = _prep(t, "t"), _prep(w, "w")
+    t, w = _lib.prep(t, "t", TAKES), _lib.prep(w, "w", TAKES)
     if t.ndim < 1 or w.ndim < 1 or t.shape[:-1] != w.shape[:-1] or t.shape[-1] != w.shape[-1] + 1:
         raise ValueError(f"lossfun_distortion: t [..., S+1] and w [..., S] expected, got {tuple(t.shape)} and {tuple(w.shape)}")
     S = w.shape[-1]
@@ -207,7 +200,7 @@ def lossfun_outer(t: Tensor, w: Tensor, t_env: Tensor, w_env: Tensor) -> Tensor:
     """The proposal loss of one level: how far the histogram (t, w) [..., S+1], [..., S] pokes out of its envelope (t_env, w_env)
     [..., P+1], [..., P].  Returns the per-ray MEAN over the S samples, [...] (nerfstudio's function returns the [..., S] terms and its
     caller takes the mean over everything; with equal S per ray the two agree).  Only ``w_env`` gets a gradient."""
-    t, w, t_env, w_env = _prep(t, "t"), _prep(w, "w"), _prep(t_env, "t_env"), _prep(w_env, "w_env")
+    t, w, t_env, w_env = _lib.prep(t, "t", TAKES), _lib.prep(w, "w", TAKES), _lib.prep(t_env, "t_env", TAKES), _lib.prep(w_env, "w_env", TAKES)
     lead = w.shape[:-1]
     if (t.shape[:-1] != lead or t_env.shape[:-1] != lead or w_env.shape[:-1] != lead or t.shape[-1] != w.shape[-1] + 1
             or t_env.shape[-1] != w_env.shape[-1] + 1):
@@ -223,7 +216,7 @@ def lossfun_outer(t: Tensor, w: Tensor, t_env: Tensor, w_env: Tensor) -> Tensor:
 def outer(t: Tensor, t_env: Tensor, w_env: Tensor) -> Tensor:
     """nerfstudio's ``outer``: for every interval of t [..., S+1] the sum of the envelope's weights w_env [..., P] over the intervals of
     t_env [..., P+1] it touches, [..., S].  For inspection and tests: no gradient."""
-    t, t_env, w_env = _prep(t, "t").detach(), _prep(t_env, "t_env").detach(), _prep(w_env, "w_env").detach()
+    t, t_env, w_env = _lib.prep(t, "t", TAKES).detach(), _lib.prep(t_env, "t_env", TAKES).detach(), _lib.prep(w_env, "w_env", TAKES).detach()
     lead = w_env.shape[:-1]
     if t.shape[:-1] != lead or t_env.shape[:-1] != lead or t_env.shape[-1] != w_env.shape[-1] + 1 or t.shape[-1] < 2:
         raise ValueError(f"outer: t [..., S+1], t_env [..., P+1], w_env [..., P] expected, got {tuple(t.shape)}, {tuple(t_env.shape)}, "

@@ -26,21 +26,9 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 
 MAX_LAYERS, MAX_DIM = _lib.SN_MLP_MAX_LAYERS, _lib.SN_MLP_MAX_DIM
+# (the kernels move single fp32 elements: any fp32 tensor's 4-byte alignment is all the entry points ask for)
+TAKES = "the MLP kernels take fp32 points and fp32 weights"
 WG_POINTS, MAX_PARTIALS = 64, 256   # csrc/sn_mlp.h: the backward kernel's point tile and its cap on partial gradient images
-
-
-def _typed(x, name: str) -> None:
-    if not isinstance(x, Tensor):
-        raise TypeError(f"{name}: a torch.Tensor expected, got {type(x).__name__}")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{name}: fp32 expected, got {x.dtype} (the MLP kernels take fp32 points and fp32 weights)")
-
-
-def _prep(x, name: str) -> Tensor:
-    _typed(x, name)
-    if not x.is_cuda:
-        raise _lib.SignerfHipError(f"{name} must live on the GPU (there is no CPU path)")
-    return x.contiguous()   # (the kernels move single fp32 elements: any fp32 tensor's 4-byte alignment is all the entry points ask for)
 
 
 def check_dims(dims: Sequence[int]) -> None:
@@ -118,7 +106,7 @@ class _FusedMLP(torch.autograd.Function):
         want_x, want_w = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:])
         if not (want_x or want_w):
             return (None,) * (1 + len(params))
-        g = _prep(g.to(torch.float32), "grad_y")
+        g = _lib.prep(g.to(torch.float32), "grad_y", TAKES)
         g_x, g_w, g_b = _backward(x, g, ctx.dims, weights, biases, want_x, want_w)
         out = [g_x]
         for i in range(len(weights)):
@@ -132,8 +120,8 @@ def _check(x, weights, biases):
         raise ValueError(f"fused_mlp: as many weights as biases, at least one, expected; got {len(weights)} and {len(biases)}")
     named = [(x, "x")] + [(w, f"weights[{i}]") for i, w in enumerate(weights)] + [(b, f"biases[{i}]") for i, b in enumerate(biases)]
     for t, name in named:   # every dtype before any device
-        _typed(t, name)
-    x, *rest = [_prep(t, name) for t, name in named]
+        _lib.typed(t, name, TAKES)
+    x, *rest = [_lib.prep(t, name, TAKES) for t, name in named]
     weights, biases = rest[:len(weights)], rest[len(weights):]
     if x.ndim < 1:
         raise ValueError("fused_mlp: x [..., d_0] expected, got a scalar")
@@ -171,7 +159,7 @@ def mlp_backward(x: Tensor, weights: Sequence[Tensor], biases: Sequence[Tensor],
                  want_grad_params: bool = True):
     """The backward entry point as it is, for tests and measurements -> (grad_x or None, [grad_W...] or None, [grad_b...] or None)."""
     x, weights, biases, dims = _check(x, weights, biases)
-    grad_y = _prep(grad_y, "grad_y").detach()
+    grad_y = _lib.prep(grad_y, "grad_y", TAKES).detach()
     N = x.numel() // dims[0]
     if grad_y.numel() != N * dims[-1]:
         raise ValueError(f"mlp_backward: grad_y [..., {dims[-1]}] for {N} points expected, got {tuple(grad_y.shape)}")

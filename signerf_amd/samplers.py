@@ -30,17 +30,8 @@ from .cameras import Frustums, RayBundle, RaySamples
 
 MAX_SAMPLES = 1024
 SPACING_MODES = {"piecewise": 0, "uniform": 1}
+TAKES = "the sampler kernels take fp32 rays, bins and weights"
 _GRIDS: dict = {}   # (kind, n, device) -> the uploaded linspace
-
-
-def _prep(x, name: str) -> Tensor:
-    if not isinstance(x, Tensor):
-        raise TypeError(f"{name}: a torch.Tensor expected, got {type(x).__name__}")
-    if x.dtype != torch.float32:
-        raise TypeError(f"{name}: fp32 expected, got {x.dtype} (the sampler kernels take fp32 rays, bins and weights)")
-    if not x.is_cuda:
-        raise _lib.SignerfHipError(f"{name} must live on the GPU (there is no CPU path)")
-    return x.detach().contiguous()
 
 
 def _count(n, what: str) -> int:
@@ -70,15 +61,15 @@ class _Rays:
             if x.dtype != torch.float32:
                 raise TypeError(f"ray_bundle.{name}: fp32 expected, got {x.dtype}")
         self.shape = tuple(b.origins.shape[:-1])
-        self.origins = _prep(b.origins, "ray_bundle.origins").reshape(-1, 3)
-        self.directions = _prep(b.directions, "ray_bundle.directions").reshape(-1, 3)
+        self.origins = _lib.prep(b.origins, "ray_bundle.origins", TAKES).detach().reshape(-1, 3)
+        self.directions = _lib.prep(b.directions, "ray_bundle.directions", TAKES).detach().reshape(-1, 3)
         self.R = self.origins.shape[0]
         if self.directions.shape[0] != self.R:
             raise ValueError("ray_bundle: origins and directions of one shape expected")
         self.device = self.origins.device
         # a bundle without nears / fars: the collider's planes (NearFarCollider while training: near = near_plane)
-        self.nears = None if b.nears is None else _prep(b.nears, "ray_bundle.nears").reshape(-1)
-        self.fars = None if b.fars is None else _prep(b.fars, "ray_bundle.fars").reshape(-1)
+        self.nears = None if b.nears is None else _lib.prep(b.nears, "ray_bundle.nears", TAKES).detach().reshape(-1)
+        self.fars = None if b.fars is None else _lib.prep(b.fars, "ray_bundle.fars", TAKES).detach().reshape(-1)
         for t, name in ((self.nears, "nears"), (self.fars, "fars")):
             if t is not None and t.numel() != self.R:
                 raise ValueError(f"ray_bundle.{name}: one value per ray expected")
@@ -93,7 +84,7 @@ def _launch(rays: _Rays, S: int, spacing_mode: str, single_jitter: bool, rand: O
         raise ValueError(f"spacing_mode={spacing_mode!r}: one of {sorted(SPACING_MODES)} expected")
     R, dev = rays.R, rays.device
     if rand is not None:
-        rand = _prep(rand, "rand")
+        rand = _lib.prep(rand, "rand", TAKES).detach()
         want = (R,) if single_jitter else (R, S + 1)
         if rand.numel() != math.prod(want) or rand.device != dev:
             raise ValueError(f"rand: a tensor {list(want)} on {dev} expected, got {tuple(rand.shape)} on {rand.device}")
@@ -156,7 +147,7 @@ def sample_pdf(ray_bundle: RayBundle, ray_samples: RaySamples, weights: Tensor, 
     if not (anneal >= 0.0) or not math.isfinite(anneal):
         raise ValueError(f"sample_pdf: anneal must be finite and >= 0, got {anneal!r}")
     rays = _Rays(ray_bundle, near_plane, far_plane)
-    weights = _prep(weights, "weights")
+    weights = _lib.prep(weights, "weights", TAKES).detach()
     if ray_samples.spacing_starts is None or ray_samples.spacing_ends is None:
         raise ValueError("sample_pdf: the ray samples carry no spacing_starts / spacing_ends")
     if weights.ndim < 2 or weights.shape[-1] != 1:
@@ -166,7 +157,7 @@ def sample_pdf(ray_bundle: RayBundle, ray_samples: RaySamples, weights: Tensor, 
     prev = getattr(ray_samples, "spacing_bins", None)
     if prev is None:
         prev = torch.cat([ray_samples.spacing_starts[..., 0], ray_samples.spacing_ends[..., -1:, 0]], dim=-1)
-    prev = _prep(prev, "ray_samples.spacing_starts").reshape(-1, N + 1)
+    prev = _lib.prep(prev, "ray_samples.spacing_starts", TAKES).detach().reshape(-1, N + 1)
     if weights.shape[0] != rays.R or prev.shape[0] != rays.R:
         raise ValueError(f"sample_pdf: weights and ray samples for {rays.R} rays expected")
     return _launch(rays, S, spacing_mode, bool(single_jitter), rand, int(seed), int(offset), return_rand,

@@ -28,16 +28,16 @@ def _check_points(q, hash_table, scalings, log2_hashmap_size, weights, biases, w
     """hashgrid's and mlp's own checks in their order (every dtype, then every device, then shapes), and dims[0] == L * F."""
     weights, biases = list(weights), list(biases)
     for x, name in ((q, "q"), (hash_table, "hash_table"), (scalings, "scalings")):
-        hashgrid._typed(x, name)
+        _lib.typed(x, name, hashgrid.TAKES)
     for i, w in enumerate(weights):
-        mlp._typed(w, f"weights[{i}]")
+        _lib.typed(w, f"weights[{i}]", mlp.TAKES)
     for i, b in enumerate(biases):
-        mlp._typed(b, f"biases[{i}]")
+        _lib.typed(b, f"biases[{i}]", mlp.TAKES)
     for x, name in ((q, "q"), (hash_table, "hash_table"), (scalings, "scalings")):   # every device before any shape
         if not x.is_cuda:
             raise _lib.SignerfHipError(f"{name} must live on the GPU (there is no CPU path)")
-    weights = [mlp._prep(w, f"weights[{i}]").detach() for i, w in enumerate(weights)]
-    biases = [mlp._prep(b, f"biases[{i}]").detach() for i, b in enumerate(biases)]
+    weights = [_lib.prep(w, f"weights[{i}]", mlp.TAKES).detach() for i, w in enumerate(weights)]
+    biases = [_lib.prep(b, f"biases[{i}]", mlp.TAKES).detach() for i, b in enumerate(biases)]
     q, hash_table, scalings = hashgrid._check(q, hash_table, scalings, log2_hashmap_size)
     if len(weights) != len(biases) or not weights:
         raise ValueError(f"{who}: as many weights as biases, at least one, expected; got {len(weights)} and {len(biases)}")
@@ -136,8 +136,8 @@ def _check_rays(weights, normals, pred_normals, directions, who: str):
     named = [(weights, "weights"), (normals, "normals")] + ([(pred_normals, "pred_normals")] if pred_normals is not None else []) + \
             ([(directions, "directions")] if directions is not None else [])
     for x, name in named:   # every dtype before any device
-        mlp._typed(x, name)
-    named = [(mlp._prep(x, name), name) for x, name in named]
+        _lib.typed(x, name, mlp.TAKES)
+    named = [(_lib.prep(x, name, mlp.TAKES), name) for x, name in named]
     weights, normals = named[0][0], named[1][0]
     pred_normals = named[2][0] if pred_normals is not None else None
     directions = named[-1][0] if directions is not None else None
@@ -163,7 +163,7 @@ def _normal_terms(weights: Tensor, normals: Tensor, pred_normals: Tensor, direct
     ``pred_normal`` is differentiable once in ``pred_normals``; nothing else carries a gradient (the weights and the analytic normals are
     detached in nerfacto's call, and the shaded normals are not read by any loss)."""
     for x, name in ((weights, "weights"), (normals, "normals"), (pred_normals, "pred_normals"), (directions, "directions")):
-        mlp._typed(x, name)
+        _lib.typed(x, name, mlp.TAKES)
     weights, normals, pred_normals, directions, lead, S = _check_rays(weights, normals, pred_normals, directions, "_normal_terms")
     orientation, pred, rn, rpn = _NormalTerms.apply(weights.detach().reshape(-1, S), normals.detach().reshape(-1, S, 3),
                                                     pred_normals.reshape(-1, S, 3), directions.detach().reshape(-1, 3))

@@ -497,8 +497,7 @@ if __name__ == "__main__":
 
     def run(key, fn, over, env):
         spec = [(k, over.get(k, v)) for k, v in DEFAULTS[fn]]
-        table, = [t for k, t in vars(_lib).items() if k.endswith("SIGNATURES") and fn in t]
-        types = table[fn][1]
+        types = _lib.functions(recorded=True)[fn][1]
         assert len(types) == len(spec) + 1, fn      # (+ the stream)
         named, alive, args = {}, [], []
         for (k, v), t in zip(spec, types):      # plain numbers first: the size queries refer to them by name

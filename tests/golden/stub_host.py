@@ -5,7 +5,7 @@
 host._lib    signerf_amd/_lib.py, loaded by path as signerf_amd._lib (the package itself would import torch)
 host.wc      tests/weights_cases.py
 host.stub    the stub, built with its version script under the soname the library asks for and loaded first, so that it serves the request
-host.lib     the library, every entry point of _lib's signature tables it exports given its ctypes signature
+host.lib     the library, every entry point of _lib's recorded headers it exports given its ctypes signature
 host.args    {kernel: [bytes of each explicit argument]} from the metadata of the library's gfx950 code object, also handed to the stub,
              which needs them to log a launch's arguments (kernel_args=False: neither is done)
 host.dev(n)  n bytes of the stub's arena"""
@@ -63,11 +63,10 @@ def boot(lib_path, kernel_args=True):
     stub.stub_launch_raw_args.restype = C.c_size_t
     stub.stub_launch_raw_args.argtypes = [C.c_int, C.c_void_p, C.c_size_t]
     lib = C.CDLL(lib_path)
-    for table in (v for k, v in sorted(vars(_lib).items()) if k.endswith("SIGNATURES")):
-        for name, (res, argtypes) in table.items():
-            fn = getattr(lib, name, None)      # (a reference commit's library may be older than a companion header)
-            if fn is not None:
-                fn.restype, fn.argtypes = res, argtypes
+    for name, (res, argtypes) in _lib.functions(recorded=True).items():
+        fn = getattr(lib, name, None)      # (a reference commit's library may be older than a companion header)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, argtypes
     for name, sizes in args.items():
         stub.stub_set_kernel_args(name.encode(), len(sizes), (C.c_uint32 * len(sizes))(*sizes))
 

@@ -1,36 +1,85 @@
-"""CPU-side checks of the drop-in boundary: the C-ABI library builds for gfx950, loads, exports every symbol that
-include/signerf_hip.h declares, and the ctypes mirrors of its structs have the C layout.  No compute calls."""
+"""CPU-side checks of the drop-in boundary: the C-ABI library builds for gfx950, loads, exports every symbol that the public headers
+under include/ declare, _lib's registry of those headers agrees with them and with the build, load() refuses a library that does not fit
+the registry, and the ctypes mirrors of the structs have the C layout.  No compute calls."""
 import ctypes as C
 import os
 import re
 import subprocess
-import tempfile
 
 import pytest
 
+from abi_helpers import INCLUDE, declared, exported
 from helpers import ROOT
 from signerf_amd import _lib
 
-HEADER = os.path.join(ROOT, "include", "signerf_hip.h")
+KEYS = [h.key for h in _lib.REGISTRY]
 
 
-def _declared_functions():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(sn_[a-z_0-9]+)\s*\(", src)))
+@pytest.mark.parametrize("key", KEYS)
+def test_header_binding_exports_version_and_build_agree(built_lib, key):
+    """One registry entry against its header file, the built library and the build's dependency list."""
+    from signerf_amd import build
+
+    h = _lib.header(key)
+    assert declared(os.path.join(INCLUDE, h.file)) == sorted(h.functions)
+    assert not sorted(set(h.functions) - exported(built_lib))
+    assert h.version_fn in h.functions and getattr(C.CDLL(built_lib), h.version_fn)() == h.version      # (not load(): it checks them all)
+    assert os.path.join("..", "..", "include", h.file) in build.HEADERS
 
 
-def test_header_and_binding_agree():
-    assert _declared_functions() == sorted(_lib.SIGNATURES.keys())
+def test_every_name_is_in_one_header_and_every_header_is_registered():
+    names = [n for h in _lib.REGISTRY for n in h.functions]
+    assert not sorted(n for n in set(names) if names.count(n) > 1)
+    assert len(_lib.functions()) == len(names) and set(_lib.functions(True)) | set(_lib.functions(False)) == set(names)
+    assert len(set(KEYS)) == len(KEYS) == 14
+    assert sorted(h.file for h in _lib.REGISTRY) == sorted(os.listdir(INCLUDE))
 
 
-def test_library_exports_every_declared_symbol(built_lib):
-    out = subprocess.run(["nm", "-D", "--defined-only", built_lib], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r" T (sn_[a-z_0-9]+)", out))
-    assert set(_declared_functions()) <= exported
-    lib = _lib.load()
-    for name in _declared_functions():
-        assert getattr(lib, name) is not None
+@pytest.fixture
+def fresh_load(monkeypatch):
+    """load() as a first call would run it; the cached handle and the registry are put back afterwards."""
+    monkeypatch.setattr(_lib, "_lib", None)
+    return monkeypatch
+
+
+@pytest.mark.parametrize("key", KEYS)
+def test_load_refuses_a_library_of_another_version(built_lib, fresh_load, key):
+    h = _lib.header(key)
+    fresh_load.setattr(_lib, "REGISTRY", tuple(x._replace(version=x.version + 7) if x.key == key else x for x in _lib.REGISTRY))
+    with pytest.raises(_lib.SignerfHipError) as e:
+        _lib.load()
+    assert f"reports {h.version_macro} {h.version}, this binding was written for {h.version + 7}: rebuild the library" in str(e.value)
+    assert _lib._lib is None
+
+
+def test_load_refuses_a_library_without_a_bound_function(built_lib, fresh_load):
+    h = _lib.header("optim")
+    fresh_load.setattr(_lib, "REGISTRY", _lib.REGISTRY[:-1] + (h._replace(functions=dict(h.functions, sn_no_such_entry_point=(C.c_int, []))),))
+    with pytest.raises(_lib.SignerfHipError, match="does not export sn_no_such_entry_point: .* rebuild it"):
+        _lib.load()
+    assert _lib._lib is None
+
+
+def test_shared_tensor_checks_raise_their_texts_in_order():
+    """_lib.typed / _lib.prep, which the wrapper modules share: not a tensor, not fp32 (with the caller's remark), not on the GPU."""
+    import torch
+
+    for check in (_lib.typed, _lib.prep):
+        with pytest.raises(TypeError) as e:
+            check([0.0], "x", "the kernels take fp32")
+        assert str(e.value) == "x: a torch.Tensor expected, got list"
+        with pytest.raises(TypeError) as e:
+            check(torch.zeros(2, dtype=torch.float64), "x", "the kernels take fp32")
+        assert str(e.value) == "x: fp32 expected, got torch.float64 (the kernels take fp32)"
+    assert _lib.typed(torch.zeros(2), "x", "") is None
+    with pytest.raises(_lib.SignerfHipError) as e:
+        _lib.prep(torch.zeros(2), "x", "")
+    assert str(e.value) == "x must live on the GPU (there is no CPU path)"
+
+
+def test_load_after_the_refusals_is_the_plain_one(built_lib):
+    assert _lib.load().sn_abi_version() == _lib.SN_ABI_VERSION and _lib.header("optim").version == 1
+    assert "sn_no_such_entry_point" not in _lib.functions()
 
 
 def test_library_contains_gfx950_code_object(built_lib):
@@ -166,8 +215,8 @@ def test_every_entry_point_survives_null_arguments(built_lib):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "scripts", "null_arguments.py")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
     got = dict(ln.split() for ln in r.stdout.splitlines() if len(ln.split()) == 2)
-    declared = set(_declared_functions()) - {"sn_create", "sn_abi_version"}
-    assert declared <= set(got) | {"sn_create"} and got["sn_create_null"] == "1", sorted(declared - set(got))
+    core = set(_lib.header("core").functions) - {"sn_create", "sn_abi_version"}
+    assert core <= set(got) | {"sn_create"} and got["sn_create_null"] == "1", sorted(core - set(got))
     special = {"sn_destroy": "0", "sn_last_error": "True", "sn_workspace_bytes": "0", "sn_mask_workspace_bytes": "0", "sn_effective_precision": "-1"}
     for name, st in got.items():
         assert st == special.get(name, "1"), (name, st)

@@ -3,15 +3,13 @@ hand-derived gradient formulas (what csrc/sn_hashgrid.h implements) against ``to
 oracle's int64 one, the companion C header include/signerf_hip_hashgrid.h against the binding, the library's exports and its argument
 refusals (in a child process: nothing is launched), and the Python surface that needs no device.  No GPU."""
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import hashgrid_oracle as ho
+from abi_helpers import c99_probe, refusal_sweep
 from helpers import ROOT, onf
 from signerf_amd import _lib
 from signerf_amd.nerfacto import MLP, HashEncoding, MLPWithHashEncoding
@@ -88,34 +86,21 @@ NAMES = ["sn_hashgrid_abi_version", "sn_hashgrid_backward", "sn_hashgrid_debug_r
 KERNELS = ["sn_hashgrid_forward_kernel", "sn_hashgrid_backward_table_kernel", "sn_hashgrid_backward_input_kernel"]
 
 
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    src = re.sub(r'#include\s+"[^"]+"', "", src)
-    return sorted(set(re.findall(r"\b(sn_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_hashgrid_header_binding_and_exports_agree(built_lib):
-    assert _declared(HEADER) == sorted(_lib.HASHGRID_BINDINGS) == NAMES
-    others = {n for k, t in vars(_lib).items() if k.endswith("SIGNATURES") for n in t}
-    assert not set(NAMES) & others
-    out = subprocess.run(["nm", "-D", "--defined-only", built_lib], capture_output=True, text=True, check=True).stdout
-    assert set(NAMES) <= set(re.findall(r" T (sn_[a-z_0-9]+)", out))
+    """(The header against the binding, the exports and build.HEADERS: tests/test_cabi.py, for every header.)"""
+    assert sorted(_lib.header("hashgrid").functions) == NAMES
     lib = _lib.load()
-    assert lib.sn_hashgrid_abi_version() == _lib.SN_HASHGRID_ABI_VERSION == 1
+    assert lib.sn_hashgrid_abi_version() == _lib.header("hashgrid").version == 1
     blob = open(built_lib, "rb").read()
     for k in KERNELS:
         assert 24 <= len(k) <= 99       # (names behind _Z23...: DESIGN.md §4 "Wide fields", "Kernel names")
         for F in (1, 2, 4, 8):
             assert ("_Z%d%sILi%dE" % (len(k), k, F)).encode() in blob
-    assert os.path.join("..", "..", "include", "signerf_hip_hashgrid.h") in __import__("signerf_amd.build", fromlist=["x"]).HEADERS
 
 
 def test_hashgrid_header_compiles_as_c99(tmp_path):
-    (tmp_path / "h.c").write_text('#include <stdio.h>\n#include "signerf_hip_hashgrid.h"\n'
-                                  'int main(void) { printf("%d %d %d\\n", SN_HASHGRID_ABI_VERSION, SN_HASHGRID_MAX_LEVELS, SN_HASHGRID_MAX_LOG2_T); return 0; }\n')
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(tmp_path / "h.c"), "-o", str(tmp_path / "h")],
-                   check=True)
-    assert subprocess.run([str(tmp_path / "h")], capture_output=True, text=True, check=True).stdout.split() == ["1", "32", "24"]
+    assert c99_probe(tmp_path, "signerf_hip_hashgrid.h", "%d %d %d",
+                     "SN_HASHGRID_ABI_VERSION, SN_HASHGRID_MAX_LEVELS, SN_HASHGRID_MAX_LOG2_T") == ["1", "32", "24"]
 
 
 _SWEEP = r"""
@@ -158,9 +143,7 @@ for k, f in calls.items():
 def test_hashgrid_entry_points_refuse_bad_arguments_before_the_device(built_lib):
     """A value outside its range, a table of 2^31 elements, a NULL required pointer, a misaligned row pointer: SN_ERR_INVALID with the entry
     point's name in sn_last_error; N = 0 is SN_OK without a launch.  In a child process -- a crash would be a segfault -- and host-only."""
-    r = subprocess.run([sys.executable, "-c", _SWEEP, ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
-    got = dict(ln.split() for ln in r.stdout.splitlines() if len(ln.split()) == 2)
+    got = refusal_sweep(_SWEEP)
     want = {k: ("0:text" if k.startswith("ok_") else "1:text") for k in got}
     want["abi"] = "1:text"
     assert len(got) == 52 and got == want

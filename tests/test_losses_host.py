@@ -4,14 +4,12 @@ include/signerf_hip_losses.h against the binding, the library's exports and its 
 launched).  No GPU."""
 import math
 import os
-import re
-import subprocess
-import sys
 
 import pytest
 import torch
 
 import loss_oracle as lo
+from abi_helpers import c99_probe, refusal_sweep
 from helpers import ROOT
 from signerf_amd import _lib
 
@@ -137,33 +135,18 @@ NAMES = ["sn_loss_composite_backward", "sn_loss_composite_forward", "sn_loss_dis
          "sn_loss_interlevel_backward", "sn_loss_interlevel_forward", "sn_losses_abi_version"]
 
 
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    src = re.sub(r'#include\s+"[^"]+"', "", src)
-    return sorted(set(re.findall(r"\b(sn_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_losses_header_binding_and_exports_agree(built_lib):
-    assert _declared(HEADER) == sorted(_lib.LOSSES_SIGNATURES) == NAMES
-    others = (set(_lib.SIGNATURES) | set(_lib.MESH_SIGNATURES) | set(_lib.MESH_COLOR_SIGNATURES) | set(_lib.MESH_RAYS_SIGNATURES)
-              | set(_lib.MESH_MATERIAL_SIGNATURES) | set(_lib.RAY_BATCH_SIGNATURES) | set(_lib.PNG_SIGNATURES))
-    assert not set(_lib.LOSSES_SIGNATURES) & others
-    out = subprocess.run(["nm", "-D", "--defined-only", built_lib], capture_output=True, text=True, check=True).stdout
-    assert set(NAMES) <= set(re.findall(r" T (sn_[a-z_0-9]+)", out))
+    """(The header against the binding, the exports and build.HEADERS: tests/test_cabi.py, for every header.)"""
+    assert sorted(_lib.header("losses").functions) == NAMES
     lib = _lib.load()
-    assert lib.sn_losses_abi_version() == _lib.SN_LOSSES_ABI_VERSION == 1
+    assert lib.sn_losses_abi_version() == _lib.header("losses").version == 1
     blob = open(built_lib, "rb").read()
     for k in [n + "_kernel" for n in NAMES if n != "sn_losses_abi_version"]:
         assert 24 <= len(k) <= 99 and k.encode() in blob       # (names behind _Z23...: DESIGN.md §4 "Wide fields", "Kernel names")
-    assert os.path.join("..", "..", "include", "signerf_hip_losses.h") in __import__("signerf_amd.build", fromlist=["x"]).HEADERS
 
 
 def test_losses_header_compiles_as_c99(tmp_path):
-    (tmp_path / "l.c").write_text('#include <stdio.h>\n#include "signerf_hip_losses.h"\n'
-                                  'int main(void) { printf("%d %d\\n", SN_LOSSES_ABI_VERSION, SN_LOSSES_MAX_SAMPLES); return 0; }\n')
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(tmp_path / "l.c"), "-o", str(tmp_path / "l")],
-                   check=True)
-    assert subprocess.run([str(tmp_path / "l")], capture_output=True, text=True, check=True).stdout.split() == ["1", "1024"]
+    assert c99_probe(tmp_path, "signerf_hip_losses.h", "%d %d", "SN_LOSSES_ABI_VERSION, SN_LOSSES_MAX_SAMPLES") == ["1", "1024"]
 
 
 _SWEEP = r"""
@@ -216,9 +199,7 @@ for k, f in calls.items():
 def test_loss_entry_points_refuse_bad_arguments_before_the_device(built_lib):
     """S or P outside [1, 1024], a negative R, a NULL required pointer: SN_ERR_INVALID with the entry point's name in sn_last_error; R = 0 is
     SN_OK without a launch.  In a child process -- a crash would be a segfault -- and host-only: it runs without a GPU."""
-    r = subprocess.run([sys.executable, "-c", _SWEEP, ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
-    got = dict(ln.split() for ln in r.stdout.splitlines() if len(ln.split()) == 2)
+    got = refusal_sweep(_SWEEP)
     want = {k: ("0:text" if k.startswith("ok_") else "1:text") for k in got}
     assert len(got) == 58 and got == want
 

@@ -4,8 +4,6 @@ No GPU."""
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,52 +11,32 @@ import torch
 
 import mesh_color_oracle as mco
 import mesh_oracle as mo
+from abi_helpers import c99_probe, refusal_sweep
 from helpers import ROOT
 from signerf_amd import _lib
 from signerf_amd.renderer import RendererConfig, load_obj, shade_defaults
 
-COLOR_HEADER = os.path.join(ROOT, "include", "signerf_hip_mesh_color.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "pyrender")
 
 
 # ---- the companion C header ------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    src = re.sub(r'#include\s+"[^"]+"', "", src)
-    return sorted(set(re.findall(r"\b(sn_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_mesh_color_header_binding_and_exports_agree(built_lib):
-    assert _declared(COLOR_HEADER) == sorted(_lib.MESH_COLOR_SIGNATURES)
-    assert not set(_lib.MESH_COLOR_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.MESH_SIGNATURES))
-    out = subprocess.run(["nm", "-D", "--defined-only", built_lib], capture_output=True, text=True, check=True).stdout
-    assert set(_lib.MESH_COLOR_SIGNATURES) <= set(re.findall(r" T (sn_[a-z_0-9]+)", out))
+    """(The header against the binding, the exports and build.HEADERS: tests/test_cabi.py, for every header.)"""
     lib = _lib.load()
-    assert lib.sn_mesh_color_abi_version() == _lib.SN_MESH_COLOR_ABI_VERSION == 1
-    assert lib.sn_mesh_abi_version() == _lib.SN_MESH_ABI_VERSION == 1   # the depth header is untouched
+    assert lib.sn_mesh_color_abi_version() == _lib.header("mesh_color").version == 1
+    assert lib.sn_mesh_abi_version() == _lib.header("mesh").version == 1   # the depth header is untouched
     blob = open(built_lib, "rb").read()
     assert b"sn_mesh_tile_color_kernel" in blob and b"sn_mask_condition_combined_kernel" in blob
-    assert os.path.join("..", "..", "include", "signerf_hip_mesh_color.h") in __import__("signerf_amd.build", fromlist=["x"]).HEADERS
 
 
 def test_shade_opts_layout_matches_c(tmp_path):
-    prog = r"""
-#include <stdio.h>
-#include <stddef.h>
-#include "signerf_hip_mesh_color.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %d\n", sizeof(SnMeshShadeOpts), offsetof(SnMeshShadeOpts, struct_size), offsetof(SnMeshShadeOpts, base_color),
-         offsetof(SnMeshShadeOpts, ambient), offsetof(SnMeshShadeOpts, background), offsetof(SnMeshShadeOpts, gamma), SN_MESH_COLOR_ABI_VERSION);
-  return 0;
-}
-"""
-    (tmp_path / "l.c").write_text(prog)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(tmp_path / "l.c"), "-o", str(tmp_path / "l")],
-                   check=True)
-    got = [int(x) for x in subprocess.run([str(tmp_path / "l")], capture_output=True, text=True, check=True).stdout.split()]
+    got = [int(x) for x in c99_probe(tmp_path, "signerf_hip_mesh_color.h", "%zu %zu %zu %zu %zu %zu %d",
+                                     "sizeof(SnMeshShadeOpts), offsetof(SnMeshShadeOpts, struct_size), offsetof(SnMeshShadeOpts, base_color), "
+                                     "offsetof(SnMeshShadeOpts, ambient), offsetof(SnMeshShadeOpts, background), "
+                                     "offsetof(SnMeshShadeOpts, gamma), SN_MESH_COLOR_ABI_VERSION")]
     o = _lib.SnMeshShadeOpts
     assert got == [C.sizeof(o), o.struct_size.offset, o.base_color.offset, o.ambient.offset, o.background.offset, o.gamma.offset,
-                   _lib.SN_MESH_COLOR_ABI_VERSION]
+                   _lib.header("mesh_color").version]
     assert _lib.SnMeshShadeOpts().struct_size == C.sizeof(o)
 
 
@@ -122,9 +100,7 @@ for k, f in calls.items():
 def test_mesh_color_entry_points_refuse_bad_arguments_before_the_device(built_lib):
     """NULL pointers, unset / too-new struct_size, non-finite shading, bad planes / intrinsics / sizes, no workspace: refused with a
     status (size queries: 0) in a child process -- a crash would be a segfault, not an exception."""
-    r = subprocess.run([sys.executable, "-c", _NULL_SWEEP, ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
-    got = dict(ln.split() for ln in r.stdout.splitlines() if len(ln.split()) == 2)
+    got = refusal_sweep(_NULL_SWEEP)
     want = {k: "1" for k in got}
     want.update({"sn_mesh_color_abi_version": "1", "sn_mesh_color_workspace_bytes": "0", "sn_mesh_color_workspace_bytes_big": "0",
                  "raster_ws": "4", "raster_ws_small": "4", "comb_ws": "4"})

@@ -2,20 +2,14 @@
 header (include/signerf_hip_mesh.h) against the binding and the library's exports, and the generator config.  No GPU."""
 import ctypes as C
 import math
-import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import mesh_oracle as mo
-from helpers import ROOT
+from abi_helpers import c99_probe, refusal_sweep
 from signerf_amd import _lib
 from signerf_amd.renderer import RendererConfig, load_obj, model_view, object_pose
-
-MESH_HEADER = os.path.join(ROOT, "include", "signerf_hip_mesh.h")
 
 
 # ---- load_obj ------------------------------------------------------------------------------------------------------------------------
@@ -203,40 +197,20 @@ def test_oracle_random_soup_against_brute_force():
 
 
 # ---- the companion C header ------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    src = re.sub(r'#include\s+"[^"]+"', "", src)
-    return sorted(set(re.findall(r"\b(sn_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_mesh_header_binding_and_exports_agree(built_lib):
-    assert _declared(MESH_HEADER) == sorted(_lib.MESH_SIGNATURES)
-    assert not set(_lib.MESH_SIGNATURES) & set(_lib.SIGNATURES)
-    out = subprocess.run(["nm", "-D", "--defined-only", built_lib], capture_output=True, text=True, check=True).stdout
-    assert set(_lib.MESH_SIGNATURES) <= set(re.findall(r" T (sn_[a-z_0-9]+)", out))
+    """(The header against the binding and the exports: tests/test_cabi.py, for every header.)"""
     lib = _lib.load()
-    assert lib.sn_mesh_abi_version() == _lib.SN_MESH_ABI_VERSION == 1
+    assert lib.sn_mesh_abi_version() == _lib.header("mesh").version == 1
     blob = open(built_lib, "rb").read()
     assert b"sn_mesh_tile_kernel" in blob and b"sn_shape_condition_kernel" in blob
 
 
 def test_mesh_opts_layout_matches_c(tmp_path):
-    prog = r"""
-#include <stdio.h>
-#include <stddef.h>
-#include "signerf_hip_mesh.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %d\n", sizeof(SnMeshRasterOpts), offsetof(SnMeshRasterOpts, struct_size), offsetof(SnMeshRasterOpts, znear),
-         offsetof(SnMeshRasterOpts, zfar), offsetof(SnMeshRasterOpts, cull_back_faces), SN_MESH_ABI_VERSION);
-  return 0;
-}
-"""
-    (tmp_path / "l.c").write_text(prog)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(tmp_path / "l.c"), "-o", str(tmp_path / "l")],
-                   check=True)
-    got = [int(x) for x in subprocess.run([str(tmp_path / "l")], capture_output=True, text=True, check=True).stdout.split()]
+    got = [int(x) for x in c99_probe(tmp_path, "signerf_hip_mesh.h", "%zu %zu %zu %zu %zu %d",
+                                     "sizeof(SnMeshRasterOpts), offsetof(SnMeshRasterOpts, struct_size), offsetof(SnMeshRasterOpts, znear), "
+                                     "offsetof(SnMeshRasterOpts, zfar), offsetof(SnMeshRasterOpts, cull_back_faces), SN_MESH_ABI_VERSION")]
     o = _lib.SnMeshRasterOpts
-    assert got == [C.sizeof(o), o.struct_size.offset, o.znear.offset, o.zfar.offset, o.cull_back_faces.offset, _lib.SN_MESH_ABI_VERSION]
+    assert got == [C.sizeof(o), o.struct_size.offset, o.znear.offset, o.zfar.offset, o.cull_back_faces.offset, _lib.header("mesh").version]
     assert _lib.SnMeshRasterOpts().struct_size == C.sizeof(o)
 
 
@@ -278,9 +252,7 @@ for k, f in calls.items():
 def test_mesh_entry_points_refuse_bad_arguments_before_the_device(built_lib):
     """NULL pointers, unset / too-new struct_size, bad planes / intrinsics, no workspace: refused with a status (size queries: 0) in a
     child process -- a crash would be a segfault, not an exception."""
-    r = subprocess.run([sys.executable, "-c", _NULL_SWEEP, ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
-    got = dict(ln.split() for ln in r.stdout.splitlines() if len(ln.split()) == 2)
+    got = refusal_sweep(_NULL_SWEEP)
     want = {"sn_mesh_abi_version": "1", "sn_mesh_workspace_bytes": "0", "sn_mesh_workspace_bytes_big": "0", "sn_mesh_raster_depth": "1",
             "sn_mesh_raster_depth_no_mesh": "1", "sn_mesh_raster_depth_size0": "1", "sn_mesh_raster_depth_newer": "1",
             "sn_mesh_raster_depth_znear": "1", "sn_mesh_raster_depth_fx": "1", "sn_mesh_raster_depth_ws": "4", "sn_shape_mask_condition": "1",

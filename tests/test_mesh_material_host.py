@@ -9,8 +9,6 @@ constants of ``material_defaults`` are UNPINNED until then.
 import ctypes as C
 import os
 import re
-import subprocess
-import sys
 import warnings
 
 import numpy as np
@@ -19,12 +17,12 @@ import pytest
 import mesh_material_oracle as mmo
 import mesh_oracle as mo
 import mesh_rays_oracle as mro
+from abi_helpers import c99_probe, refusal_sweep
 from helpers import ROOT
 from signerf_amd import _lib
 from signerf_amd import renderer as R
 from signerf_amd.renderer import Renderer, RendererConfig, load_mtl, load_obj, load_obj_materials, material_defaults, object_pose, pack_materials
 
-HEADER = os.path.join(ROOT, "include", "signerf_hip_mesh_material.h")
 
 OBJ = """# a quad and two triangles
 mtllib two.mtl
@@ -220,41 +218,24 @@ def test_setup_reads_no_mtl_for_none(tmp_path):
 
 
 # ---- the companion C header ----------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    src = re.sub(r'#include\s+"[^"]+"', "", src)
-    return sorted(set(re.findall(r"\b(sn_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_material_header_binding_and_exports_agree(built_lib):
-    assert _declared(HEADER) == sorted(_lib.MESH_MATERIAL_SIGNATURES)
-    assert not set(_lib.MESH_MATERIAL_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.MESH_SIGNATURES) | set(_lib.MESH_COLOR_SIGNATURES)
-                                                     | set(_lib.MESH_RAYS_SIGNATURES))
-    out = subprocess.run(["nm", "-D", "--defined-only", built_lib], capture_output=True, text=True, check=True).stdout
-    assert set(_lib.MESH_MATERIAL_SIGNATURES) <= set(re.findall(r" T (sn_[a-z_0-9]+)", out))
+    """(The header against the binding, the exports and build.HEADERS: tests/test_cabi.py, for every header.)"""
     lib = _lib.load()
-    assert lib.sn_mesh_material_abi_version() == _lib.SN_MESH_MATERIAL_ABI_VERSION == 1
+    assert lib.sn_mesh_material_abi_version() == _lib.header("mesh_material").version == 1
     assert lib.sn_mesh_abi_version() == 1 and lib.sn_mesh_color_abi_version() == 1 and lib.sn_mesh_rays_abi_version() == 1   # untouched
     blob = open(built_lib, "rb").read()
     assert b"sn_mesh_tile_material_kernel" in blob and b"sn_mesh_rays_material_kernel" in blob
-    assert os.path.join("..", "..", "include", "signerf_hip_mesh_material.h") in __import__("signerf_amd.build", fromlist=["x"]).HEADERS
 
 
 def test_material_structs_layout_matches_c(tmp_path):
     rec = ["base_color", "texel_offset", "tex_width", "tex_height", "reserved"]
     mats = ["struct_size", "n_materials", "materials", "host_materials", "triangle_material", "corner_uv", "texels", "texel_bytes", "texture_srgb",
             "reserved"]
-    prog = "#include <stdio.h>\n#include <stddef.h>\n#include \"signerf_hip_mesh_material.h\"\nint main(void) {\n"
-    prog += '  printf("%zu %zu %d\\n", sizeof(SnMeshMaterial), sizeof(SnMeshMaterials), SN_MESH_MATERIAL_ABI_VERSION);\n'
-    prog += "".join(f'  printf("%zu\\n", offsetof(SnMeshMaterial, {k}));\n' for k in rec)
-    prog += "".join(f'  printf("%zu\\n", offsetof(SnMeshMaterials, {k}));\n' for k in mats)
-    prog += "  return 0;\n}\n"
-    (tmp_path / "l.c").write_text(prog)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(tmp_path / "l.c"), "-o", str(tmp_path / "l")],
-                   check=True)
-    got = [int(x) for x in subprocess.run([str(tmp_path / "l")], capture_output=True, text=True, check=True).stdout.split()]
+    exprs = ["sizeof(SnMeshMaterial)", "sizeof(SnMeshMaterials)", "SN_MESH_MATERIAL_ABI_VERSION"] + \
+            [f"offsetof(SnMeshMaterial, {k})" for k in rec] + [f"offsetof(SnMeshMaterials, {k})" for k in mats]
+    got = [int(x) for x in c99_probe(tmp_path, "signerf_hip_mesh_material.h", "%zu %zu %d" + " %zu" * (len(rec) + len(mats)), ", ".join(exprs))]
     a, b = _lib.SnMeshMaterial, _lib.SnMeshMaterials
-    want = [C.sizeof(a), C.sizeof(b), _lib.SN_MESH_MATERIAL_ABI_VERSION] + [getattr(a, k).offset for k in rec] + [getattr(b, k).offset for k in mats]
+    want = [C.sizeof(a), C.sizeof(b), _lib.header("mesh_material").version] + [getattr(a, k).offset for k in rec] + [getattr(b, k).offset for k in mats]
     assert got == want and C.sizeof(a) == 32
     assert _lib.SnMeshMaterials().struct_size == C.sizeof(b)
 
@@ -339,9 +320,7 @@ def test_material_calls_refuse_bad_arguments_before_the_device(built_lib):
     """NULL where not allowed, M outside [1, 65535], a texture side outside [1, 16384], a texel blob smaller than the (host copy of the)
     records claim, a struct_size of 0 or of a newer layout: refused with SN_ERR_INVALID (the workspace: SN_ERR_WORKSPACE) and a text, in
     a child process -- nothing is launched (every pointer is a fake), and a crash would be a segfault, not an exception."""
-    r = subprocess.run([sys.executable, "-c", _NULL_SWEEP, ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
-    got = dict(ln.split() for ln in r.stdout.splitlines() if len(ln.split()) == 2)
+    got = refusal_sweep(_NULL_SWEEP)
     want = {k: "1" for k in got}
     want["raster_no_workspace"] = "4"
     assert len(got) == 1 + 2 * 21 + 4 and got == want, got

@@ -36,21 +36,16 @@ These errors are the conditioning of the depth of a grazing triangle, not the ke
 differ only by the fp32 rounding of the rays, are 6.7e-06 / 7.4e-06 / 9.2e-06 / 4.9e-06 apart.
 """
 import ctypes as C
-import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import mesh_oracle as mo
 import mesh_rays_oracle as mro
-from helpers import ROOT
+from abi_helpers import c99_probe, refusal_sweep
 from signerf_amd import _lib
 from signerf_amd.renderer import ACCEL_LEAF_MAX, Renderer, RendererConfig, build_accel, object_pose
 
-RAYS_HEADER = os.path.join(ROOT, "include", "signerf_hip_mesh_rays.h")
 EPS, Z_RTOL = mro.EPS, mro.Z_RTOL
 
 
@@ -97,41 +92,21 @@ def test_setup_builds_the_accel_only_for_the_camera_lens(tmp_path):
 
 
 # ---- the companion C header ------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    src = re.sub(r'#include\s+"[^"]+"', "", src)
-    return sorted(set(re.findall(r"\b(sn_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_mesh_rays_header_binding_and_exports_agree(built_lib):
-    assert _declared(RAYS_HEADER) == sorted(_lib.MESH_RAYS_SIGNATURES)
-    assert not set(_lib.MESH_RAYS_SIGNATURES) & (set(_lib.SIGNATURES) | set(_lib.MESH_SIGNATURES) | set(_lib.MESH_COLOR_SIGNATURES))
-    out = subprocess.run(["nm", "-D", "--defined-only", built_lib], capture_output=True, text=True, check=True).stdout
-    assert set(_lib.MESH_RAYS_SIGNATURES) <= set(re.findall(r" T (sn_[a-z_0-9]+)", out))
+    """(The header against the binding, the exports and build.HEADERS: tests/test_cabi.py, for every header.)"""
     lib = _lib.load()
-    assert lib.sn_mesh_rays_abi_version() == _lib.SN_MESH_RAYS_ABI_VERSION == 1
+    assert lib.sn_mesh_rays_abi_version() == _lib.header("mesh_rays").version == 1
     assert lib.sn_mesh_abi_version() == 1 and lib.sn_mesh_color_abi_version() == 1   # the two raster headers are untouched
     assert b"sn_mesh_rays_kernel" in open(built_lib, "rb").read()
-    assert os.path.join("..", "..", "include", "signerf_hip_mesh_rays.h") in __import__("signerf_amd.build", fromlist=["x"]).HEADERS
 
 
 def test_rays_opts_layout_matches_c(tmp_path):
-    prog = r"""
-#include <stdio.h>
-#include <stddef.h>
-#include "signerf_hip_mesh_rays.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %d\n", sizeof(SnMeshRaysOpts), offsetof(SnMeshRaysOpts, struct_size), offsetof(SnMeshRaysOpts, znear),
-         offsetof(SnMeshRaysOpts, zfar), offsetof(SnMeshRaysOpts, cull_back_faces), SN_MESH_RAYS_ABI_VERSION);
-  return 0;
-}
-"""
-    (tmp_path / "l.c").write_text(prog)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(tmp_path / "l.c"), "-o", str(tmp_path / "l")],
-                   check=True)
-    got = [int(x) for x in subprocess.run([str(tmp_path / "l")], capture_output=True, text=True, check=True).stdout.split()]
+    got = [int(x) for x in c99_probe(tmp_path, "signerf_hip_mesh_rays.h", "%zu %zu %zu %zu %zu %d",
+                                     "sizeof(SnMeshRaysOpts), offsetof(SnMeshRaysOpts, struct_size), offsetof(SnMeshRaysOpts, znear), "
+                                     "offsetof(SnMeshRaysOpts, zfar), offsetof(SnMeshRaysOpts, cull_back_faces), SN_MESH_RAYS_ABI_VERSION")]
     o = _lib.SnMeshRaysOpts
-    assert got == [C.sizeof(o), o.struct_size.offset, o.znear.offset, o.zfar.offset, o.cull_back_faces.offset, _lib.SN_MESH_RAYS_ABI_VERSION]
+    assert got == [C.sizeof(o), o.struct_size.offset, o.znear.offset, o.zfar.offset, o.cull_back_faces.offset,
+                   _lib.header("mesh_rays").version]
     assert _lib.SnMeshRaysOpts().struct_size == C.sizeof(o)
 
 
@@ -188,9 +163,7 @@ for k, f in calls.items():
 def test_cast_rays_refuses_bad_arguments_before_the_device(built_lib):
     """NULL pointers (the accel blob among them), a struct_size of 0 or of a newer layout, bad planes / sizes / blob sizes: refused with
     SN_ERR_INVALID (size queries: 0) in a child process -- nothing is launched, and a crash would be a segfault, not an exception."""
-    r = subprocess.run([sys.executable, "-c", _NULL_SWEEP, ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
-    got = dict(ln.split() for ln in r.stdout.splitlines() if len(ln.split()) == 2)
+    got = refusal_sweep(_NULL_SWEEP)
     want = {k: "1" for k in got}
     want.update({"abi": "1", "accel_bytes_negative": "0", "accel_bytes_too_many": "0"})
     assert len(got) == 22 and got == want

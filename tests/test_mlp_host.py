@@ -6,17 +6,16 @@ import ctypes as C
 import os
 import re
 import subprocess
-import sys
 
 import pytest
 import torch
 
 import mlp_oracle as mo
-from helpers import ROOT, onf, small_config
+from abi_helpers import c99_probe, refusal_sweep
+from helpers import onf, small_config
 from signerf_amd import _lib, mlp
 from signerf_amd.nerfacto import MLP
 
-HEADER = os.path.join(ROOT, "include", "signerf_hip_mlp.h")
 D = torch.float64
 INTEGER_SIZES = [17, 130, 1000]
 
@@ -77,36 +76,22 @@ NAMES = ["sn_mlp_abi_version", "sn_mlp_backward", "sn_mlp_backward_workspace_byt
 KERNELS = ["sn_train_mlp_forward_kernel", "sn_train_mlp_backward_kernel", "sn_train_mlp_reduce_kernel"]
 
 
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    src = re.sub(r'#include\s+"[^"]+"', "", src)
-    return sorted(set(re.findall(r"\b(sn_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_mlp_header_binding_and_exports_agree(built_lib):
-    assert _declared(HEADER) == sorted(_lib.MLP_BINDINGS) == NAMES
-    others = {n for k, t in vars(_lib).items() if (k.endswith("SIGNATURES") or k.endswith("BINDINGS")) and k != "MLP_BINDINGS" for n in t}
-    assert not set(NAMES) & others
-    out = subprocess.run(["nm", "-D", "--defined-only", built_lib], capture_output=True, text=True, check=True).stdout
-    assert set(NAMES) <= set(re.findall(r" T (sn_[a-z_0-9]+)", out))
+    """(The header against the binding, the exports and build.HEADERS: tests/test_cabi.py, for every header.)"""
+    assert sorted(_lib.header("mlp").functions) == NAMES
     lib = _lib.load()
-    assert lib.sn_mlp_abi_version() == _lib.SN_MLP_ABI_VERSION == 1
+    assert lib.sn_mlp_abi_version() == _lib.header("mlp").version == 1
     blob = open(built_lib, "rb").read()
     for k in KERNELS:
         assert 24 <= len(k) <= 99       # (names behind _Z23...: DESIGN.md §4 "Wide fields", "Kernel names")
         assert ("_Z%d%s11SnMlpParams" % (len(k), k)).encode() in blob
-    assert os.path.join("..", "..", "include", "signerf_hip_mlp.h") in __import__("signerf_amd.build", fromlist=["x"]).HEADERS
     assert (mlp.MAX_LAYERS, mlp.MAX_DIM) == (4, 64)
 
 
 def test_mlp_header_compiles_as_c99_and_the_descriptor_has_the_bindings_layout(tmp_path):
-    (tmp_path / "h.c").write_text('#include <stdio.h>\n#include <stddef.h>\n#include "signerf_hip_mlp.h"\n'
-                                  'int main(void) { printf("%d %d %d %d %d %d %d\\n", SN_MLP_ABI_VERSION, SN_MLP_MAX_LAYERS, SN_MLP_MAX_DIM, '
-                                  '(int)sizeof(SnMlpDesc), (int)offsetof(SnMlpDesc, weights), (int)offsetof(SnMlpDesc, grad_weights), '
-                                  '(int)offsetof(SnMlpDesc, grad_biases)); return 0; }\n')
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(tmp_path / "h.c"), "-o", str(tmp_path / "h")],
-                   check=True)
-    got = subprocess.run([str(tmp_path / "h")], capture_output=True, text=True, check=True).stdout.split()
+    got = c99_probe(tmp_path, "signerf_hip_mlp.h", "%d %d %d %d %d %d %d",
+                    "SN_MLP_ABI_VERSION, SN_MLP_MAX_LAYERS, SN_MLP_MAX_DIM, (int)sizeof(SnMlpDesc), (int)offsetof(SnMlpDesc, weights), "
+                    "(int)offsetof(SnMlpDesc, grad_weights), (int)offsetof(SnMlpDesc, grad_biases)")
     S = _lib.SnMlpDesc
     assert got == [str(v) for v in (1, 4, 64, C.sizeof(S), S.weights.offset, S.grad_weights.offset, S.grad_biases.offset)]
     assert _lib.SnMlpDesc().struct_size == C.sizeof(S) == 160
@@ -175,9 +160,7 @@ def test_mlp_entry_points_refuse_bad_arguments_before_the_device(built_lib):
     """N < 0, N >= 2^31, a layer count or a width out of range, an unknown struct_size, a NULL required pointer, half a gradient group, a
     short or missing workspace, a misaligned pointer: SN_ERR_INVALID with the entry point's name in sn_last_error (the workspace query
     answers 0); N = 0 is SN_OK without a launch.  In a child process -- a crash would be a segfault -- and host-only."""
-    r = subprocess.run([sys.executable, "-c", _SWEEP, ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
-    got = dict(ln.split() for ln in r.stdout.splitlines() if len(ln.split()) == 2)
+    got = refusal_sweep(_SWEEP)
     want = {k: ("0:text" if k.startswith("ok_") else "1:text") for k in got}
     assert len(got) == 1 + 2 * 23 + 16 and got == want
 

@@ -6,14 +6,13 @@ import ctypes as C
 import os
 import re
 import subprocess
-import sys
 
 import pytest
 
+from abi_helpers import c99_probe, refusal_sweep
 from helpers import ROOT
 from signerf_amd import _lib
 
-HEADER = os.path.join(ROOT, "include", "signerf_hip_optim.h")
 SRC = os.path.join(ROOT, "tests", "c", "optim_plan.cpp")
 NAMES = ["sn_adam_step", "sn_adam_workspace_bytes", "sn_optim_abi_version"]
 KERNELS = ["sn_optim_adam_stats_kernel", "sn_optim_adam_prologue_kernel", "sn_optim_adam_update_kernel"]
@@ -69,25 +68,15 @@ def test_workspace_size_is_the_headers_layout(built_lib, exe, n_tensors, total):
 
 
 # ---- the companion C header ------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    src = re.sub(r'#include\s+"[^"]+"', "", src)
-    return sorted(set(re.findall(r"\b(sn_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_optim_header_binding_and_exports_agree(built_lib):
-    assert _declared(HEADER) == sorted(_lib.OPTIM_BINDINGS) == NAMES
-    others = {n for k, t in vars(_lib).items() if (k.endswith("SIGNATURES") or k.endswith("BINDINGS")) and k != "OPTIM_BINDINGS" for n in t}
-    assert not set(NAMES) & others
-    out = subprocess.run(["nm", "-D", "--defined-only", built_lib], capture_output=True, text=True, check=True).stdout
-    assert set(NAMES) <= set(re.findall(r" T (sn_[a-z_0-9]+)", out))
+    """(The header against the binding, the exports and build.HEADERS: tests/test_cabi.py, for every header.)"""
+    assert sorted(_lib.header("optim").functions) == NAMES
     lib = _lib.load()
-    assert lib.sn_optim_abi_version() == _lib.SN_OPTIM_ABI_VERSION == 1
+    assert lib.sn_optim_abi_version() == _lib.header("optim").version == 1
     blob = open(built_lib, "rb").read()
     for k in KERNELS:
         assert 24 <= len(k) <= 99       # (names behind _Z23...: DESIGN.md §4 "Wide fields", "Kernel names")
         assert ("_Z%d%s10SnAdamArgs" % (len(k), k)).encode() in blob
-    assert os.path.join("..", "..", "include", "signerf_hip_optim.h") in __import__("signerf_amd.build", fromlist=["x"]).HEADERS
 
 
 def test_optim_header_compiles_as_c99_and_the_structs_have_the_bindings_layout(tmp_path):
@@ -95,12 +84,8 @@ def test_optim_header_compiles_as_c99_and_the_structs_have_the_bindings_layout(t
     fields += [("SnAdamGroup", f) for f in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_norm")]
     fields += [("SnAdamRecord", f) for f in ("skip", "grad_multiplier", "step_size", "sqrt_bc2", "grad_norm")]
     structs = ("SnAdamTensor", "SnAdamGroup", "SnAdamRecord")
-    body = "".join('printf("%%d\\n", (int)sizeof(%s));' % s for s in structs) + "".join('printf("%%d\\n", (int)offsetof(%s, %s));' % sf for sf in fields)
-    (tmp_path / "h.c").write_text('#include <stdio.h>\n#include <stddef.h>\n#include "signerf_hip_optim.h"\n'
-                                  'int main(void) { printf("%d %d\\n", SN_OPTIM_ABI_VERSION, SN_ADAM_MAX_TENSORS); ' + body + " return 0; }\n")
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(tmp_path / "h.c"), "-o", str(tmp_path / "h")],
-                   check=True)
-    got = subprocess.run([str(tmp_path / "h")], capture_output=True, text=True, check=True).stdout.split()
+    exprs = ["SN_OPTIM_ABI_VERSION", "SN_ADAM_MAX_TENSORS"] + ["(int)sizeof(%s)" % s for s in structs] + ["(int)offsetof(%s, %s)" % sf for sf in fields]
+    got = c99_probe(tmp_path, "signerf_hip_optim.h", " ".join(["%d"] * len(exprs)), ", ".join(exprs))
     want = [1, 32] + [C.sizeof(getattr(_lib, s)) for s in structs] + [getattr(getattr(_lib, s), f).offset for s, f in fields]
     assert got == [str(v) for v in want]
     assert _lib.SnAdamTensor().struct_size == C.sizeof(_lib.SnAdamTensor) == 64 and _lib.SnAdamGroup().struct_size == 28
@@ -186,9 +171,7 @@ def test_adam_step_refuses_bad_arguments_before_the_device(built_lib):
     eps < 0, a NaN hyper-parameter, an unknown struct_size, a missing, short or misaligned workspace: SN_ERR_INVALID with the entry point's
     name in sn_last_error; no tensors and only empty tensors are SN_OK without a launch and without a look at the pointers.  In a child
     process -- a crash would be a segfault -- and host-only."""
-    r = subprocess.run([sys.executable, "-c", _SWEEP, ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
-    got = dict(ln.split() for ln in r.stdout.splitlines() if len(ln.split()) == 2)
+    got = refusal_sweep(_SWEEP)
     want = {k: ("0:text" if k.startswith("ok_") else "1:text") for k in got}
     assert len(got) == 54 and got == want
 

@@ -5,13 +5,13 @@ the binding and the library's exports, and the refusals of ``sn_png_encode`` (in
 import os
 import re
 import subprocess
-import sys
 import zlib
 
 import numpy as np
 import pytest
 
 import png_cases as pc
+from abi_helpers import refusal_sweep
 from helpers import ROOT
 from signerf_amd import _lib, dataset_io
 
@@ -113,24 +113,13 @@ def test_refused_shapes_have_no_plan(builds):
 
 
 # ---- the companion C header ------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    src = re.sub(r'#include\s+"[^"]+"', "", src)
-    return sorted(set(re.findall(r"\b(sn_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_png_header_binding_and_exports_agree(built_lib):
-    assert _declared(HEADER) == sorted(_lib.PNG_SIGNATURES) == ["sn_png_abi_version", "sn_png_encode", "sn_png_max_file_bytes",
-                                                                "sn_png_segment_bytes", "sn_png_workspace_bytes"]
-    others = (set(_lib.SIGNATURES) | set(_lib.MESH_SIGNATURES) | set(_lib.MESH_COLOR_SIGNATURES) | set(_lib.MESH_RAYS_SIGNATURES)
-              | set(_lib.MESH_MATERIAL_SIGNATURES) | set(_lib.RAY_BATCH_SIGNATURES))
-    assert not set(_lib.PNG_SIGNATURES) & others
-    out = subprocess.run(["nm", "-D", "--defined-only", built_lib], capture_output=True, text=True, check=True).stdout
-    assert set(_lib.PNG_SIGNATURES) <= set(re.findall(r" T (sn_[a-z_0-9]+)", out))
+    """(The header against the binding, the exports and build.HEADERS: tests/test_cabi.py, for every header.)"""
+    assert sorted(_lib.header("png").functions) == ["sn_png_abi_version", "sn_png_encode", "sn_png_max_file_bytes", "sn_png_segment_bytes",
+                                                    "sn_png_workspace_bytes"]
     lib = _lib.load()
-    assert lib.sn_png_abi_version() == _lib.SN_PNG_ABI_VERSION == 1
+    assert lib.sn_png_abi_version() == _lib.header("png").version == 1
     assert lib.sn_png_segment_bytes() == pc.S
-    assert os.path.join("..", "..", "include", "signerf_hip_png.h") in __import__("signerf_amd.build", fromlist=["x"]).HEADERS
     blob = open(built_lib, "rb").read()
     names = set(re.findall(rb"_Z\d+(sn_png_[a-z_]+_kernel)", blob))
     assert names == {b"sn_png_segment_deflate_kernel", b"sn_png_finish_file_kernel", b"sn_png_compact_bytes_kernel"}
@@ -174,9 +163,7 @@ for k, f in calls.items():
 
 
 def test_png_encode_refuses_bad_arguments_before_the_device(built_lib):
-    r = subprocess.run([sys.executable, "-c", _SWEEP, ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
-    got = dict(ln.split() for ln in r.stdout.splitlines() if len(ln.split()) == 2)
+    got = refusal_sweep(_SWEEP)
     assert len(got) == 15 and got == {k: "1:text" for k in got}
 
 

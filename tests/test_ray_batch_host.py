@@ -1,59 +1,31 @@
 """Ray batches across cameras, CPU side: the companion C header include/signerf_hip_ray_batch.h against the binding and the library's
 exports, the argument checks of ``sn_generate_ray_batch`` (in a child process: nothing is launched), the pixel samplers of
 signerf_amd/data.py on ``device="cpu"`` and the host-side argument errors of ``Cameras.generate_rays``.  No GPU."""
-import os
-import re
-import subprocess
-import sys
 
 import pytest
 import torch
 
-from helpers import ROOT
+from abi_helpers import c99_probe, refusal_sweep
 from signerf_amd import Cameras, CameraType, PatchPixelSampler, PatchPixelSamplerConfig, PixelSampler, PixelSamplerConfig, _lib
-
-HEADER = os.path.join(ROOT, "include", "signerf_hip_ray_batch.h")
 
 
 # ---- the companion C header ------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    src = re.sub(r'#include\s+"[^"]+"', "", src)
-    return sorted(set(re.findall(r"\b(sn_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_ray_batch_header_binding_and_exports_agree(built_lib):
-    assert _declared(HEADER) == sorted(_lib.RAY_BATCH_SIGNATURES) == ["sn_generate_ray_batch", "sn_ray_batch_abi_version"]
-    others = (set(_lib.SIGNATURES) | set(_lib.MESH_SIGNATURES) | set(_lib.MESH_COLOR_SIGNATURES) | set(_lib.MESH_RAYS_SIGNATURES)
-              | set(_lib.MESH_MATERIAL_SIGNATURES))
-    assert not set(_lib.RAY_BATCH_SIGNATURES) & others
-    out = subprocess.run(["nm", "-D", "--defined-only", built_lib], capture_output=True, text=True, check=True).stdout
-    assert set(_lib.RAY_BATCH_SIGNATURES) <= set(re.findall(r" T (sn_[a-z_0-9]+)", out))
+    """(The header against the binding, the exports and build.HEADERS: tests/test_cabi.py, for every header.)"""
+    assert sorted(_lib.header("ray_batch").functions) == ["sn_generate_ray_batch", "sn_ray_batch_abi_version"]
     lib = _lib.load()
-    assert lib.sn_ray_batch_abi_version() == _lib.SN_RAY_BATCH_ABI_VERSION == 1
+    assert lib.sn_ray_batch_abi_version() == _lib.header("ray_batch").version == 1
     assert b"sn_ray_batch_kernel" in open(built_lib, "rb").read()
-    assert os.path.join("..", "..", "include", "signerf_hip_ray_batch.h") in __import__("signerf_amd.build", fromlist=["x"]).HEADERS
 
 
 def test_camera_record_is_26_dwords(tmp_path):
     """The device camera table is built as [B, 26] int32 rows (cameras.py::_camera_table): the C struct must be exactly that."""
     import ctypes as C
 
-    prog = r"""
-#include <stdio.h>
-#include <stddef.h>
-#include "signerf_hip_ray_batch.h"
-int main(void) {
-  printf("%zu %zu %zu %zu %zu %zu %zu %d\n", sizeof(SnCameraDesc), offsetof(SnCameraDesc, fx), offsetof(SnCameraDesc, height),
-         offsetof(SnCameraDesc, width), offsetof(SnCameraDesc, camera_type), offsetof(SnCameraDesc, has_distortion),
-         offsetof(SnCameraDesc, distortion), SN_RAY_BATCH_ABI_VERSION);
-  return 0;
-}
-"""
-    (tmp_path / "l.c").write_text(prog)
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(tmp_path / "l.c"), "-o", str(tmp_path / "l")],
-                   check=True)
-    got = [int(x) for x in subprocess.run([str(tmp_path / "l")], capture_output=True, text=True, check=True).stdout.split()]
+    got = [int(x) for x in c99_probe(tmp_path, "signerf_hip_ray_batch.h", "%zu %zu %zu %zu %zu %zu %zu %d",
+                                     "sizeof(SnCameraDesc), offsetof(SnCameraDesc, fx), offsetof(SnCameraDesc, height), "
+                                     "offsetof(SnCameraDesc, width), offsetof(SnCameraDesc, camera_type), "
+                                     "offsetof(SnCameraDesc, has_distortion), offsetof(SnCameraDesc, distortion), SN_RAY_BATCH_ABI_VERSION")]
     d = _lib.SnCameraDesc
     assert got == [104, 48, 64, 68, 72, 76, 80, 1]
     assert got[:7] == [C.sizeof(d), d.fx.offset, d.height.offset, d.width.offset, d.camera_type.offset, d.has_distortion.offset, d.distortion.offset]
@@ -99,9 +71,7 @@ for k, f in calls.items():
 def test_generate_ray_batch_refuses_bad_arguments_before_the_device(built_lib):
     """NULL mandatory pointers, both index forms together, neither, img_c = 5, pixels with the coords form, ...: SN_ERR_INVALID with text in
     sn_last_error, in a child process -- nothing is launched (n = 0 is SN_OK without a launch), and a crash would be a segfault."""
-    r = subprocess.run([sys.executable, "-c", _SWEEP, ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
-    got = dict(ln.split() for ln in r.stdout.splitlines() if len(ln.split()) == 2)
+    got = refusal_sweep(_SWEEP)
     want = {k: "1:text" for k in got}
     want.update({"abi": "1:text", "n_0_is_ok": "0:text", "n_0_coords_form_is_ok": "0:text"})
     assert len(got) == 18 and got == want

@@ -3,15 +3,13 @@ restatement against Random123's known-answer vectors, the companion C header inc
 library's exports and its argument refusals (in a child process: nothing is launched), the monotonicity of the restatement on the inputs
 the GPU tests use, and ``ProposalNetworkSampler``'s schedule logic with stub density functions.  No GPU."""
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
 import sampler_oracle as so
+from abi_helpers import c99_probe, refusal_sweep, struct_fields
 from helpers import ROOT, onf
 from signerf_amd import _lib
 
@@ -111,45 +109,25 @@ NAMES = ["sn_sampler_abi_version", "sn_sampler_initial", "sn_sampler_pdf"]
 KERNELS = ["sn_train_sampler_initial_kernel", "sn_train_sampler_pdf_kernel"]
 
 
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    src = re.sub(r'#include\s+"[^"]+"', "", src)
-    return sorted(set(re.findall(r"\b(sn_[a-z_0-9]+)\s*\(", src)))
-
-
-def _struct_fields(header, name):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), src, flags=re.S).group(1)
-    return [re.search(r"(\w+)\s*$", ln.strip().rstrip(";")).group(1) for ln in body.split("\n") if ln.strip()]
-
-
 def test_sampler_header_binding_and_exports_agree(built_lib):
-    assert _declared(HEADER) == sorted(_lib.SAMPLER_BINDINGS) == NAMES
-    others = {n for k, t in vars(_lib).items() if k.endswith("SIGNATURES") for n in t}
-    assert not set(NAMES) & others
-    assert _struct_fields(HEADER, "SnSamplerRays") == [f[0] for f in _lib.SnSamplerRays._fields_]
-    assert _struct_fields(HEADER, "SnSamplerPdf") == [f[0] for f in _lib.SnSamplerPdf._fields_]
-    out = subprocess.run(["nm", "-D", "--defined-only", built_lib], capture_output=True, text=True, check=True).stdout
-    assert set(NAMES) <= set(re.findall(r" T (sn_[a-z_0-9]+)", out))
+    """(The header against the binding, the exports and build.HEADERS: tests/test_cabi.py, for every header.)"""
+    assert sorted(_lib.header("sampler").functions) == NAMES
+    assert struct_fields(HEADER, "SnSamplerRays") == [f[0] for f in _lib.SnSamplerRays._fields_]
+    assert struct_fields(HEADER, "SnSamplerPdf") == [f[0] for f in _lib.SnSamplerPdf._fields_]
     lib = _lib.load()
-    assert lib.sn_sampler_abi_version() == _lib.SN_SAMPLER_ABI_VERSION == 1
+    assert lib.sn_sampler_abi_version() == _lib.header("sampler").version == 1
     blob = open(built_lib, "rb").read()
     for k in KERNELS:
         assert 24 <= len(k) <= 99       # (names behind _Z23...: DESIGN.md §4 "Kernel names")
         assert ("_Z%d%s15SnSamplerParams" % (len(k), k)).encode() in blob
-    assert os.path.join("..", "..", "include", "signerf_hip_sampler.h") in __import__("signerf_amd.build", fromlist=["x"]).HEADERS
 
 
 def test_sampler_header_compiles_as_c99(tmp_path):
-    (tmp_path / "h.c").write_text('#include <stdio.h>\n#include "signerf_hip_sampler.h"\n'
-                                  'int main(void) { printf("%d %d %d %d\\n", SN_SAMPLER_ABI_VERSION, SN_SAMPLER_MAX_SAMPLES, '
-                                  '(int)sizeof(SnSamplerRays), (int)sizeof(SnSamplerPdf)); return 0; }\n')
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(tmp_path / "h.c"), "-o", str(tmp_path / "h")],
-                   check=True)
     import ctypes as C
 
-    assert subprocess.run([str(tmp_path / "h")], capture_output=True, text=True, check=True).stdout.split() == [
-        "1", "1024", str(C.sizeof(_lib.SnSamplerRays)), str(C.sizeof(_lib.SnSamplerPdf))]
+    got = c99_probe(tmp_path, "signerf_hip_sampler.h", "%d %d %d %d",
+                    "SN_SAMPLER_ABI_VERSION, SN_SAMPLER_MAX_SAMPLES, (int)sizeof(SnSamplerRays), (int)sizeof(SnSamplerPdf)")
+    assert got == ["1", "1024", str(C.sizeof(_lib.SnSamplerRays)), str(C.sizeof(_lib.SnSamplerPdf))]
 
 
 _SWEEP = r"""
@@ -213,9 +191,7 @@ def test_sampler_entry_points_refuse_bad_arguments_before_the_device(built_lib):
     """A count outside its range, a NULL required pointer, a struct_size too small or too large, an anneal that is negative or not finite,
     n_rays < 0: SN_ERR_INVALID with the entry point's name in sn_last_error; n_rays = 0 is SN_OK without a launch.  In a child process -- a
     crash would be a segfault -- and host-only."""
-    r = subprocess.run([sys.executable, "-c", _SWEEP, ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
-    got = dict(ln.split() for ln in r.stdout.splitlines() if len(ln.split()) == 2)
+    got = refusal_sweep(_SWEEP)
     want = {k: ("0:text" if k.startswith("ok_") else "1:text") for k in got}
     want["abi"] = "1:text"
     assert len(got) == 1 + 2 * 16 + 18 and got == want

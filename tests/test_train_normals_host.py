@@ -6,7 +6,6 @@ import ctypes as C
 import os
 import re
 import subprocess
-import sys
 
 import pytest
 import torch
@@ -14,12 +13,11 @@ import torch
 import hashgrid_oracle as ho
 import mlp_oracle as mo
 import train_normals_oracle as to
-from helpers import ROOT, onf, small_config
+from abi_helpers import c99_probe, refusal_sweep
+from helpers import onf, small_config
 from signerf_amd import _lib, train_normals
 
 D = torch.float64
-HEADERS = {"train_normals": os.path.join(ROOT, "include", "signerf_hip_train_normals.h"),
-           "normal_losses": os.path.join(ROOT, "include", "signerf_hip_normal_losses.h")}
 NAMES = {"train_normals": ["sn_train_normals_abi_version", "sn_train_normals_analytic"],
          "normal_losses": ["sn_loss_normals_backward", "sn_loss_normals_forward", "sn_normal_losses_abi_version"]}
 KERNELS = ["_Z32sn_train_normals_analytic_kernelILi%dEEv20SnTrainNormalsParams" % f for f in (1, 2, 4, 8)] + \
@@ -110,42 +108,26 @@ def test_loss_formulas_and_their_gradient():
 
 
 # ---- the companion C headers ---------------------------------------------------------------------------------------------------------------
-def _declared(header):
-    src = re.sub(r"/\*.*?\*/", "", open(header).read(), flags=re.S)
-    src = re.sub(r'#include\s+"[^"]+"', "", src)
-    return sorted(set(re.findall(r"\b(sn_[a-z_0-9]+)\s*\(", src)))
-
-
 def test_headers_binding_and_exports_agree(built_lib):
-    tables = {"train_normals": _lib.TRAIN_NORMALS_BINDINGS, "normal_losses": _lib.NORMAL_LOSSES_BINDINGS}
-    for key, header in HEADERS.items():
-        assert _declared(header) == sorted(tables[key]) == NAMES[key]
-    mine = set(NAMES["train_normals"]) | set(NAMES["normal_losses"])
-    others = {n for k, t in vars(_lib).items() if (k.endswith("SIGNATURES") or k.endswith("BINDINGS")) and t not in tables.values() for n in t}
-    assert not mine & others
-    out = subprocess.run(["nm", "-D", "--defined-only", built_lib], capture_output=True, text=True, check=True).stdout
-    assert mine <= set(re.findall(r" T (sn_[a-z_0-9]+)", out))
+    """(The headers against the binding, the exports and build.HEADERS: tests/test_cabi.py, for every header.)"""
+    for key in NAMES:
+        assert sorted(_lib.header(key).functions) == NAMES[key]
     lib = _lib.load()
-    assert lib.sn_train_normals_abi_version() == _lib.SN_TRAIN_NORMALS_ABI_VERSION == 1
-    assert lib.sn_normal_losses_abi_version() == _lib.SN_NORMAL_LOSSES_ABI_VERSION == 1
+    assert lib.sn_train_normals_abi_version() == _lib.header("train_normals").version == 1
+    assert lib.sn_normal_losses_abi_version() == _lib.header("normal_losses").version == 1
     assert lib.sn_losses_abi_version() == 1 and lib.sn_mlp_abi_version() == 1 and lib.sn_hashgrid_abi_version() == 1     # (the siblings' stand)
     blob = open(built_lib, "rb").read()
     for k in KERNELS:
         assert k.encode() in blob, k
     build_headers = __import__("signerf_amd.build", fromlist=["x"]).HEADERS
-    for h in ("signerf_hip_train_normals.h", "signerf_hip_normal_losses.h"):
-        assert os.path.join("..", "..", "include", h) in build_headers
     for h in ("sn_train_normals.h", "sn_normal_losses.h", "sn_api_train_normals.h", "sn_api_normal_losses.h"):
         assert h in build_headers
 
 
 def test_headers_compile_as_c99(tmp_path):
-    (tmp_path / "h.c").write_text('#include <stdio.h>\n#include "signerf_hip_train_normals.h"\n#include "signerf_hip_normal_losses.h"\n'
-                                  'int main(void) { printf("%d %d %d %d\\n", SN_TRAIN_NORMALS_ABI_VERSION, SN_NORMAL_LOSSES_ABI_VERSION, '
-                                  'SN_LOSSES_MAX_SAMPLES, SN_MLP_MAX_DIM); return 0; }\n')
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(tmp_path / "h.c"), "-o", str(tmp_path / "h")],
-                   check=True)
-    assert subprocess.run([str(tmp_path / "h")], capture_output=True, text=True, check=True).stdout.split() == ["1", "1", "1024", "64"]
+    got = c99_probe(tmp_path, ("signerf_hip_train_normals.h", "signerf_hip_normal_losses.h"), "%d %d %d %d",
+                    "SN_TRAIN_NORMALS_ABI_VERSION, SN_NORMAL_LOSSES_ABI_VERSION, SN_LOSSES_MAX_SAMPLES, SN_MLP_MAX_DIM")
+    assert got == ["1", "1", "1024", "64"]
 
 
 _SWEEP = r"""
@@ -200,9 +182,7 @@ for k, f in calls.items():
 def test_entry_points_refuse_bad_arguments_before_the_device(built_lib):
     """What signerf_hip_hashgrid.h, signerf_hip_mlp.h and signerf_hip_losses.h refuse, and dims[0] != L * F (also at N = 0): SN_ERR_INVALID
     with the entry point's name in sn_last_error; N = 0 / R = 0 is SN_OK without a launch.  In a child process, host-only."""
-    r = subprocess.run([sys.executable, "-c", _SWEEP, ROOT], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
-    got = dict(ln.split() for ln in r.stdout.splitlines() if len(ln.split()) == 2)
+    got = refusal_sweep(_SWEEP)
     want = {k: ("0:text" if k.startswith("ok_") else "1:text") for k in got}
     assert len(got) == 26 + 10 + 8 and got == want
 
