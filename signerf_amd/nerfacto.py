@@ -10,7 +10,7 @@ and what ``SIGNeRFPipeline`` touches (/root/reference/signerf/signerf_pipeline.p
     param groups "proposal_networks" / "fields" / "camera_opt" (signerf_config.py:47-60).
 
 The modules below hold the parameters under nerfstudio's torch-path state-dict names; their arithmetic lives in
-``csrc/`` and is reached through the C ABI -- there is no PyTorch forward and no CPU fallback.
+``csrc/`` and is reached through the model's HIP handle (``signerf_amd.engine``) -- there is no PyTorch forward and no CPU fallback.
 The exception is the training-side call surface of the containers themselves: ``HashEncoding.forward`` (the HIP op of
 ``signerf_amd.hashgrid``, differentiable), ``MLP.forward`` (its ``nn.Linear`` stack as torch ops) and ``MLPWithHashEncoding.forward``;
 the eval render does not go through them.  The training forward does: ``HashMLPDensityField.get_density_training``,
@@ -22,8 +22,6 @@ from __future__ import annotations
 
 import re
 
-import ctypes as C
-import threading
 import warnings
 from typing import Dict, List, Optional
 
@@ -34,54 +32,9 @@ from torch import Tensor, nn
 from . import _lib, mlp
 from .cameras import Frustums, RaySamples, RayBundle, SceneBox  # noqa: F401
 from .config import NerfactoModelConfig, SIGNeRFModelConfig
+from .engine import BACKGROUNDS, INITIAL_SAMPLERS, PRECISIONS, Engine, wants_half_grid
 
-PRECISIONS = {"fp32": 0, "fp16x2": 1, "fp16": 2}   # "fp16": opt-in, implementation="tcnn" only (config.py)
-# RGBRenderer's background in EVAL mode [NS]: "last_sample" (nerfacto's default, what SIGNeRF runs), a named constant colour, or "random" --
-# a training device: combine_rgb returns the composited colour without a background, i.e. black
-BACKGROUNDS = {"last_sample": None, "black": (0.0, 0.0, 0.0), "white": (1.0, 1.0, 1.0), "random": (0.0, 0.0, 0.0)}
-# NerfactoModelConfig.proposal_initial_sampler [NS] -> SnRenderOpts.spacing_mode: UniformLinDispPiecewiseSampler (the default) or UniformSampler
-INITIAL_SAMPLERS = {"piecewise": 0, "uniform": 1}
 TRAINING_MLPS = ("torch", "hip")   # config.training_mlp
-
-
-class _RWLock:
-    """Many render calls, or one weight upload.  The C ABI orders uploads against renders ON THE DEVICE, but the host-side sequence
-    sn_upload_weights ... sn_finalize_weights leaves the handle un-finalized in between, so a render CALL of another thread (the viewer
-    rendering on the shared model while the generator thread reloads weights) must not start inside it.  Writers have preference: a
-    waiting upload blocks NEW readers, so a viewer that renders back to back cannot starve it."""
-
-    def __init__(self):
-        self._cond = threading.Condition()
-        self._readers = 0
-        self._writer = False
-        self._writers_waiting = 0
-
-    def acquire_read(self):
-        with self._cond:
-            while self._writer or self._writers_waiting:
-                self._cond.wait()
-            self._readers += 1
-
-    def release_read(self):
-        with self._cond:
-            self._readers -= 1
-            if self._readers == 0:
-                self._cond.notify_all()
-
-    def acquire_write(self):
-        with self._cond:
-            self._writers_waiting += 1
-            try:
-                while self._writer or self._readers:
-                    self._cond.wait()
-            finally:
-                self._writers_waiting -= 1
-            self._writer = True
-
-    def release_write(self):
-        with self._cond:
-            self._writer = False
-            self._cond.notify_all()
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -577,15 +530,7 @@ class NerfactoModel(nn.Module):
         self.num_train_data = num_train_data if num_train_data is not None else config.num_train_data
         self.kwargs = kwargs
         self.device_indicator_param = nn.Parameter(torch.empty(0))
-        self._handle = C.c_void_p(None)
-        self._handle_device = None
-        self._handle_half_grid = False   # whether the handle holds the grid's fp16 storage (SnFieldDesc.half_grid)
-        self._weights_dirty = True
-        self._engine_generation = 0      # bumped whenever the handle's weights are (re)written
-        self._weights_lock = threading.Lock()
-        self._engine_rw = _RWLock()
-        self._grid_cache: Dict = {}
-        self._fallback_warned = False
+        self._engine = Engine(self)   # the eval-mode HIP handle: a plain object that holds the model weakly (signerf_amd.engine)
         self.populate_modules()
 
     # -- module set-up (names = nerfstudio's; signerf.py:32-39 overrides this and calls super) -------------
@@ -751,7 +696,40 @@ class NerfactoModel(nn.Module):
         """Call after mutating parameters in place (e.g. an optimizer step) so the next render re-uploads them."""
         self._weights_dirty = True
 
-    # -- HIP engine ---------------------------------------------------------------------------------------------
+    # -- HIP engine (signerf_amd.engine): what code outside the package calls on the model ------------------------
+    @property
+    def _weights_dirty(self) -> bool:
+        return self._engine.dirty
+
+    @_weights_dirty.setter
+    def _weights_dirty(self, value: bool) -> None:
+        self._engine.dirty = value
+
+    @property
+    def effective_precision(self) -> str:
+        """What ``config.precision`` resolves to for the uploaded parameters (``Engine.effective_precision``)."""
+        return self._engine.effective_precision()
+
+    def _ensure_engine(self):
+        return self._engine.ensure()
+
+    def _render_normals(self, b: RayBundle, H: int, W: int, state=None) -> Dict[str, Tensor]:
+        return self._engine.render_normals(b, H, W, state)
+
+    # for tests that call the C entry points themselves, single-threaded, on a model that has rendered (they predate the engine)
+    @property
+    def _handle(self):
+        return self._engine.handle
+
+    def _opts(self, H: int, W: int, lib, single_chunk: bool = False):
+        return self._engine.opts(lib, self._engine.handle, H, W, single_chunk)
+
+    def __del__(self):
+        try:
+            self._engine.close()
+        except Exception:
+            pass
+
     def _field_desc(self) -> _lib.SnFieldDesc:
         cfg = self.config
         d = _lib.SnFieldDesc()
@@ -774,141 +752,8 @@ class NerfactoModel(nn.Module):
             d.aabb[k] = v
         d.dense_levels = int(getattr(cfg, "dense_levels", 0))
         d.dense_copy_cap_mb = int(getattr(cfg, "dense_copy_cap_mb", 0))
-        # the single-fp16 mode keeps the tiny-cuda-nn grid in fp16 storage as well (half the gather bytes; include/signerf_hip.h half_grid)
-        d.half_grid = 1 if (cfg.precision == "fp16" and cfg.implementation == "tcnn") else 0
+        d.half_grid = 1 if wants_half_grid(cfg) else 0
         return d
-
-    @property
-    def effective_precision(self) -> str:
-        """What ``config.precision`` resolves to for the uploaded parameters ("fp16x2" falls back to "fp32" for a handle whose split-
-        precision MLPs cannot be range-conditioned; sn_effective_precision)."""
-        self._engine_rw.acquire_read()
-        try:
-            if not self._handle or self._weights_dirty:
-                return self.config.precision
-            eff = _lib.load().sn_effective_precision(self._handle, PRECISIONS[self.config.precision], 0)
-        finally:
-            self._engine_rw.release_read()
-        return {0: "fp32", 1: "fp16x2", 2: "fp16"}.get(eff, self.config.precision)
-
-    def _ensure_engine(self):
-        lib = _lib.load()
-        if self.device.type != "cuda":
-            raise _lib.SignerfHipError("NerfactoModel renders on the GPU only: move it with .to('cuda') (no CPU fallback)")
-        with self._weights_lock:
-            # precision="fp16" set on a model whose handle was created without the grid's fp16 storage: start over with it (once)
-            want_half = self.config.precision == "fp16" and self.config.implementation == "tcnn"
-            stale_half = bool(self._handle) and want_half and not self._handle_half_grid
-            if (self._handle and self._handle_device != self.device) or not self._handle or self._weights_dirty or stale_half:
-                # the handle is replaced / its weights rewritten: no render CALL of another thread may hold or take the handle meanwhile
-                self._engine_rw.acquire_write()
-                try:
-                    if self._handle and (self._handle_device != self.device or stale_half):
-                        # model.to("cuda:N") after the first render: the handle and all its buffers live on the old GPU -- start over
-                        lib.sn_destroy(self._handle)
-                        self._handle = C.c_void_p(None)
-                        self._weights_dirty = True
-                        self._grid_cache.clear()
-                    if not self._handle:
-                        desc = self._field_desc()
-                        with torch.cuda.device(self.device):
-                            _lib.check(lib.sn_create(C.byref(desc), C.byref(self._handle)), None, "sn_create")
-                        self._handle_device = self.device
-                        self._handle_half_grid = bool(desc.half_grid)
-                    if self._weights_dirty:
-                        self._upload(lib)
-                        self._weights_dirty = False
-                        self._engine_generation += 1   # (a kept render state of the old weights no longer matches: _render_normals)
-                finally:
-                    self._engine_rw.release_write()
-        if not self._fallback_warned and self.effective_precision != self.config.precision:
-            self._fallback_warned = True
-            if self.config.hidden_dim == 128:   # a wide field: only the exact-fp32 MFMA arithmetic is built (DESIGN.md §4 "Wide fields")
-                why = "is not built for wide fields (hidden_dim=128)"
-            else:
-                why = "cannot hold fp32 grade for these parameters"
-            warnings.warn(f"signerf_amd: precision={self.config.precision!r} {why}; "
-                          f"rendering with {self.effective_precision!r}", RuntimeWarning, stacklevel=3)
-        return lib
-
-    def _upload(self, lib):
-        stream = _lib.current_stream()
-
-        def up(name: str, t: Tensor):
-            t = t.detach().to(torch.float32).contiguous()
-            buf = t if t.is_cuda else t.cpu()
-            _lib.check(lib.sn_upload_weights(self._handle, name.encode(), buf.data_ptr(), buf.numel() * 4, stream),
-                       self._handle, f"sn_upload_weights({name})")
-
-        with torch.cuda.device(self.device):
-            sd = self.state_dict()
-            for k, v in sd.items():
-                if (k.endswith("hash_table") or ".mlp.layers." in k or k.startswith("field.mlp_head.layers.")
-                        or (self._has_pred_normals and k.startswith(("field.mlp_pred_normals.layers.", "field.field_head_pred_normals.net.")))):
-                    up(k, v)
-            if self.config.appearance_embed_dim > 0:
-                if self.config.use_average_appearance_embedding:
-                    app = self.field.embedding_appearance.mean(0)
-                else:
-                    app = torch.zeros(self.config.appearance_embed_dim, device=self.device)
-                up("field.embedding_appearance.mean", app)
-            _lib.check(lib.sn_finalize_weights(self._handle, stream), self._handle, "sn_finalize_weights")
-            # "fp16x2" is a request: the library conditions the split-precision MLPs into fp16's range from the uploaded parameters and
-            # falls back to the exact-fp32 MFMA path for a handle it cannot condition (include/signerf_hip.h, sn_effective_precision)
-            self._fallback_warned = False
-
-    def __del__(self):
-        try:
-            if self._handle:
-                _lib.load().sn_destroy(self._handle)
-        except Exception:
-            pass
-
-    # sampler grids, computed with the same torch ops nerfstudio uses (bit-identical to the reference's)
-    def _grids(self, n_levels: int):
-        cfg = self.config
-        counts = list(cfg.num_proposal_samples_per_ray[:n_levels]) + [cfg.num_nerf_samples_per_ray]
-        key = (tuple(counts), str(self.device))
-        if key not in self._grid_cache:
-            bins0 = torch.linspace(0.0, 1.0, counts[0] + 1)
-            us = []
-            for m in counts[1:]:
-                nb = m + 1
-                u = torch.linspace(0.0, 1.0 - (1.0 / nb), steps=nb) + 1.0 / (2 * nb)
-                us.append(u.to(self.device))
-            self._grid_cache[key] = (bins0.to(self.device), us)
-        return self._grid_cache[key]
-
-    def _opts(self, H: int, W: int, lib, single_chunk: bool = False):
-        cfg = self.config
-        n_levels = cfg.num_proposal_iterations
-        o = _lib.SnRenderOpts()
-        o.num_proposal_iterations = n_levels
-        for i in range(n_levels):
-            o.num_proposal_samples[i] = cfg.num_proposal_samples_per_ray[i]
-        o.num_nerf_samples = cfg.num_nerf_samples_per_ray
-        o.near_plane = cfg.near_plane if self.training else 0.0  # NearFarCollider: eval near = 0 (A3)
-        o.far_plane = cfg.far_plane
-        # the chunk size only shapes the expected-depth clip bounds (A17): per eval_num_rays_per_chunk rays for a camera bundle
-        # (Model.get_outputs_for_camera_ray_bundle's loop), over the whole bundle for Model.get_outputs / forward
-        o.chunk_rays = max(H * W, 1) if single_chunk else cfg.eval_num_rays_per_chunk
-        o.precision = PRECISIONS[cfg.precision]
-        bg = BACKGROUNDS[cfg.background_color]
-        o.background_mode = 0 if bg is None else 1
-        o.spacing_mode = INITIAL_SAMPLERS[cfg.proposal_initial_sampler]
-        stats = getattr(self, "_march_stats", None)   # diagnostics (ops.render_with_march_stats): 3 uint64 counters the kernels add to
-        o.march_stats = stats.data_ptr() if stats is not None else None
-        for c in range(3):
-            o.background_rgb[c] = 0.0 if bg is None else bg[c]
-        bins0, us = self._grids(n_levels)
-        o.initial_spacing_bins = bins0.data_ptr()
-        for i, u in enumerate(us):
-            o.pdf_u[i] = u.data_ptr()
-        need = lib.sn_workspace_bytes(self._handle, H, W, C.byref(o))
-        ws = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
-        o.workspace = ws.data_ptr()
-        o.workspace_bytes = ws.numel()
-        return o, (ws, bins0, us)
 
     # -- rows a6-a17 ---------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -1025,7 +870,7 @@ class NerfactoModel(nn.Module):
         keep_bins = mode != "never" and self.config.num_proposal_iterations > 0 and H * W > 0
         # lazy mode: only below config.normals_bin_reuse_max_mb (the workspace then lives as long as the outputs dict does)
         cap = None if mode == "always" else int(self.config.normals_bin_reuse_max_mb) << 20
-        raw, state = self._render_ex(b, H, W, single_chunk, keep_state=keep_bins, keep_state_max_bytes=cap)
+        raw, state = self._engine.render(b, H, W, single_chunk, keep_state=keep_bins, keep_state_max_bytes=cap)
         out = {k: v.view(*shape, v.shape[-1]) for k, v in raw.items()}
         if mode == "never":
             return out
@@ -1041,95 +886,6 @@ class NerfactoModel(nn.Module):
             out.update(producer())
             return out
         return LazyOutputs(out, producer)
-
-    def _render_normals(self, b: RayBundle, H: int, W: int, state=None) -> Dict[str, Tensor]:
-        """Row a16: "normals" (analytic) and "pred_normals", [H*W,3] each, by the separate normals kernel (csrc/sn_normals.h).
-        ``state`` = what ``_render_ex(..., keep_state=True)`` kept of the colour render of the SAME bundle: its options, its workspace
-        (the final sample bins are still in it) and an event behind its kernels -- the proposal sampler is then not run again."""
-        lib = self._ensure_engine()
-        dev = self.device
-        if H * W == 0:
-            z = torch.empty((0, 3), dtype=torch.float32, device=dev)
-            return {"normals": z, "pred_normals": z.clone()} if self._has_pred_normals else {"normals": z}
-        f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-        reuse = state is not None and state["generation"] == self._engine_generation
-        # the very tensors the colour render marched (the library's workspace stamp compares their addresses: a second fp32 / contiguous
-        # copy of a bundle that needed one would be "another bundle")
-        origins, directions, nears, fars = state["rays"] if reuse else (f32(b.origins), f32(b.directions), f32(b.nears), f32(b.fars))
-        with torch.cuda.device(dev):
-            normals = torch.empty((H * W, 3), dtype=torch.float32, device=dev)
-            pred = torch.empty((H * W, 3), dtype=torch.float32, device=dev) if self._has_pred_normals else None
-            self._engine_rw.acquire_read()
-            try:
-                st = _lib.SN_ERR_STATE
-                if reuse:
-                    o, keep = state["opts"], state["keep"]
-                    o.reuse_final_bins = 1
-                    o.march_stats = None
-                    cur = torch.cuda.current_stream(dev)
-                    cur.wait_event(state["event"])            # (a viewer thread may read the normals on another stream)
-                    keep[0].record_stream(cur)
-                    st = lib.sn_render_normals(self._handle, _lib.ptr(origins), _lib.ptr(directions), _lib.ptr(nears), _lib.ptr(fars), H, W,
-                                               C.byref(o), _lib.ptr(normals), _lib.ptr(pred), _lib.current_stream())
-                    if st == _lib.SN_ERR_STATE:
-                        # the library found that the workspace no longer holds this frame's bins (weights re-uploaded in between, the
-                        # memory handed to another call): not an error for the caller -- the proposal kernel runs again
-                        msg = lib.sn_last_error(self._handle)
-                        warnings.warn("lazy normals: the kept sample bins could not be re-used (%s); running the proposal sampler again"
-                                      % (msg.decode() if msg else ""), RuntimeWarning)
-                        reuse = False
-                if not reuse:
-                    o, keep = self._opts(H, W, lib)   # (sn_workspace_bytes reads the handle: inside the read lock)
-                    o.march_stats = None              # (the colour render of this frame has counted the proposal levels already)
-                    st = lib.sn_render_normals(self._handle, _lib.ptr(origins), _lib.ptr(directions), _lib.ptr(nears), _lib.ptr(fars), H, W,
-                                               C.byref(o), _lib.ptr(normals), _lib.ptr(pred), _lib.current_stream())
-                _lib.check(st, self._handle, "sn_render_normals")
-            finally:
-                self._engine_rw.release_read()
-        return {"normals": normals, "pred_normals": pred} if pred is not None else {"normals": normals}
-
-    def _render(self, b: RayBundle, H: int, W: int, single_chunk: bool = False) -> Dict[str, Tensor]:
-        return self._render_ex(b, H, W, single_chunk)[0]
-
-    def _render_ex(self, b: RayBundle, H: int, W: int, single_chunk: bool = False, keep_state: bool = False, keep_state_max_bytes=None):
-        """-> (outputs, state).  state (``keep_state``) = {"opts", "keep" (workspace + grids), "rays", "event", "generation"} for a normals
-        launch on the same bundle that re-uses this render's final sample bins (``_render_normals``); None otherwise -- also when the
-        workspace is larger than ``keep_state_max_bytes`` (config.normals_bin_reuse_max_mb)."""
-        lib = self._ensure_engine()
-        if H * W == 0:  # an empty bundle renders to empty outputs, as the reference's chunk loop does
-            z = lambda c: torch.empty((0, c), dtype=torch.float32, device=self.device)  # noqa: E731
-            out = {"rgb": z(3), "accumulation": z(1), "depth": z(1), "expected_depth": z(1)}
-            out.update({f"prop_depth_{i}": z(1) for i in range(self.config.num_proposal_iterations)})
-            return out, None
-        dev = self.device
-        f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-        origins, directions, nears, fars = f32(b.origins), f32(b.directions), f32(b.nears), f32(b.fars)
-        n = H * W
-        with torch.cuda.device(dev):
-            new = lambda c: torch.empty((n, c), dtype=torch.float32, device=dev)  # noqa: E731
-            rgb, depth, acc, exp = new(3), new(1), new(1), new(1)
-            props = [new(1) for _ in range(self.config.num_proposal_iterations)]
-            pp = [_lib.ptr(p) for p in props] + [None] * (2 - len(props))
-            self._engine_rw.acquire_read()
-            try:
-                o, keep = self._opts(H, W, lib, single_chunk)   # (sn_workspace_bytes reads the handle: inside the read lock)
-                st = lib.sn_render_rays(self._handle, _lib.ptr(origins), _lib.ptr(directions), _lib.ptr(nears), _lib.ptr(fars), H, W,
-                                        C.byref(o), _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(exp), pp[0], pp[1],
-                                        _lib.current_stream())
-                _lib.check(st, self._handle, "sn_render_rays")
-                state = None
-                if keep_state and (keep_state_max_bytes is None or keep[0].numel() <= keep_state_max_bytes):
-                    ev = torch.cuda.Event()
-                    ev.record(torch.cuda.current_stream(dev))
-                    state = {"opts": o, "keep": keep, "rays": (origins, directions, nears, fars), "event": ev, "generation": self._engine_generation}
-            finally:
-                self._engine_rw.release_read()
-            # (the workspace and grids in `keep` are consumed by work already enqueued on this stream; the caching allocator is
-            # stream-ordered, so letting them go when this frame returns is safe)
-        out = {"rgb": rgb, "accumulation": acc, "depth": depth, "expected_depth": exp}
-        for i, p in enumerate(props):
-            out[f"prop_depth_{i}"] = p
-        return out, state
 
 
 class SIGNeRFModel(NerfactoModel):

@@ -10,6 +10,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from .engine import PRECISIONS, _f32_on
 
 
 def _f32(t: Tensor) -> Tensor:
@@ -18,22 +19,23 @@ def _f32(t: Tensor) -> Tensor:
 
 def hash_encode(model, q: Tensor, which: int = -1, return_indices: bool = False):
     """HashEncoding forward (torch-path semantics, row a13).  q [n,3] in [0,1) -> features [n, L*F] (+ table rows [n,L,8])."""
-    lib = model._ensure_engine()
+    engine = model._engine
+    engine.ensure()
     q = _f32(q)
     n = q.shape[0]
     enc = (model.field.mlp_base if which < 0 else model.proposal_networks[which].mlp_base).encoder
-    with torch.cuda.device(q.device):
+    with torch.cuda.device(q.device), engine.reading() as (lib, handle):
         feat = torch.empty((n, enc.num_levels * enc.features_per_level), dtype=torch.float32, device=q.device)
         idx = torch.empty((n, enc.num_levels, 8), dtype=torch.int32, device=q.device) if return_indices else None
-        _lib.check(lib.sn_hash_encode(model._handle, which, _lib.ptr(q), n, _lib.ptr(feat), _lib.ptr(idx), _lib.current_stream()),
-                   model._handle, "sn_hash_encode")
+        _lib.check(lib.sn_hash_encode(handle, which, _lib.ptr(q), n, _lib.ptr(feat), _lib.ptr(idx), _lib.current_stream()), handle, "sn_hash_encode")
     return (feat, idx) if return_indices else feat
 
 
 def field_forward(model, positions: Tensor, directions: Optional[Tensor] = None, which: int = -1, return_geo: bool = False):
     """NerfactoField / HashMLPDensityField on explicit world positions (rows a9, a14, a15) -> density [n], rgb [n,3] | None
     (+ the main field's geometry features [n,15] with ``return_geo``: nerfstudio's ``base_mlp_out``)."""
-    lib = model._ensure_engine()
+    engine = model._engine
+    engine.ensure()
     pos = _f32(positions)
     n = pos.shape[0]
     d = None if directions is None else _f32(directions)
@@ -41,15 +43,10 @@ def field_forward(model, positions: Tensor, directions: Optional[Tensor] = None,
         density = torch.empty((n,), dtype=torch.float32, device=pos.device)
         rgb = torch.empty((n, 3), dtype=torch.float32, device=pos.device) if (which < 0 and d is not None) else None
         geo = torch.empty((n, 15), dtype=torch.float32, device=pos.device) if return_geo else None
-        from .nerfacto import PRECISIONS
-
-        model._engine_rw.acquire_read()
-        try:
-            _lib.check(lib.sn_field_forward_geo(model._handle, which, _lib.ptr(pos), _lib.ptr(d), n, PRECISIONS[model.config.precision],
+        with engine.reading() as (lib, handle):
+            _lib.check(lib.sn_field_forward_geo(handle, which, _lib.ptr(pos), _lib.ptr(d), n, PRECISIONS[model.config.precision],
                                                 _lib.ptr(density), _lib.ptr(rgb), _lib.ptr(geo), _lib.current_stream()),
-                       model._handle, "sn_field_forward")
-        finally:
-            model._engine_rw.release_read()
+                       handle, "sn_field_forward")
     return (density, rgb, geo) if return_geo else (density, rgb)
 
 
@@ -144,17 +141,16 @@ def render_rays_debug(model, ray_bundle, want=("main_fetch", "main_q", "median_i
     "main_fetch" [H*W,S,16,8] int64 (uint32 words), "main_q" [H*W,S,3], "median_index" [H*W] int32, "prop_fetch_k" [H*W,N_k,5,8], "prop_q_k" [H*W,N_k,3],
     "pdf_index_k" [H*W,M_k+1] int32 -- see the header for the record format; with "final_bins" in `want` (a model with proposal nets)
     also "final_bins" [H*W,S+1], read from this launch's workspace as render_with_final_bins reads the production launch's."""
-    lib = model._ensure_engine()
+    engine = model._engine
+    engine.ensure()
     H, W = ray_bundle.origins.shape[:2]
     dev = model.device
     cfg = model.config
-    f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-    o, d, nears, fars = f32(ray_bundle.origins), f32(ray_bundle.directions), f32(ray_bundle.nears), f32(ray_bundle.fars)
+    o, d, nears, fars = (_f32_on(dev, t) for t in (ray_bundle.origins, ray_bundle.directions, ray_bundle.nears, ray_bundle.fars))
     n = H * W
     S = cfg.num_nerf_samples_per_ray
     nprop = cfg.num_proposal_iterations
     with torch.cuda.device(dev):
-        opts, keep = model._opts(H, W, lib)
         new = lambda c: torch.empty((n, c), dtype=torch.float32, device=dev)  # noqa: E731
         rgb, depth, acc, exp = new(3), new(1), new(1), new(1)
         dump = _lib.SnDebugDump()
@@ -179,10 +175,12 @@ def render_rays_debug(model, ray_bundle, want=("main_fetch", "main_q", "median_i
             if "pdf_index" in want:
                 t[f"pdf_index_{k}"] = torch.full((n, counts[k + 1] + 1), -1, dtype=torch.int32, device=dev)
                 dump.pdf_index[k] = t[f"pdf_index_{k}"].data_ptr()
-        st = lib.sn_render_rays_debug(model._handle, _lib.ptr(o), _lib.ptr(d), _lib.ptr(nears), _lib.ptr(fars), H, W, C.byref(opts),
-                                      _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(exp), None, None, C.byref(dump),
-                                      _lib.current_stream())
-        _lib.check(st, model._handle, "sn_render_rays_debug")
+        with engine.reading() as (lib, handle):
+            opts, keep = engine.opts(lib, handle, H, W)
+            st = lib.sn_render_rays_debug(handle, _lib.ptr(o), _lib.ptr(d), _lib.ptr(nears), _lib.ptr(fars), H, W, C.byref(opts),
+                                          _lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(acc), _lib.ptr(exp), None, None, C.byref(dump),
+                                          _lib.current_stream())
+            _lib.check(st, handle, "sn_render_rays_debug")
         torch.cuda.synchronize(dev)
         if "final_bins" in want and nprop > 0:
             t["final_bins"] = _read_final_bins(keep[0], H, W, S, cfg.eval_num_rays_per_chunk)
@@ -214,7 +212,7 @@ def render_with_final_bins(model, ray_bundle):
         raise _lib.SignerfHipError("render_with_final_bins: the model has no proposal nets (the uniform sampler's bins are its initial bins)")
     H, W = ray_bundle.origins.shape[:2]
     S = cfg.num_nerf_samples_per_ray
-    raw, state = model._render_ex(ray_bundle, H, W, False, keep_state=True)
+    raw, state = model._engine.render(ray_bundle, H, W, keep_state=True)   # (takes the read lock itself)
     torch.cuda.synchronize(model.device)
     bins = _read_final_bins(state["keep"][0], H, W, S, cfg.eval_num_rays_per_chunk)
     return {k: raw[k].view(H, W, -1) for k in ("rgb", "depth", "accumulation", "expected_depth")}, bins
@@ -230,9 +228,14 @@ def _read_final_bins(workspace: Tensor, H: int, W: int, S: int, chunk_rays: int)
 
 def debug_layout(model, which: int = -1) -> dict:
     """Layout of the derived gather buffers of one field (sn_debug_layout)."""
-    lib = model._ensure_engine()
+    model._engine.ensure()
+    with model._engine.reading() as (lib, handle):
+        return _layout(lib, handle, which)
+
+
+def _layout(lib, handle, which: int) -> dict:
     lay = _lib.SnDebugLayout()
-    _lib.check(lib.sn_debug_layout(model._handle, which, C.byref(lay)), model._handle, "sn_debug_layout")
+    _lib.check(lib.sn_debug_layout(handle, which, C.byref(lay)), handle, "sn_debug_layout")
     return {"n_dense": lay.n_dense, "n_bc": lay.n_bc, "dense_res": list(lay.dense_res), "dense_off": list(lay.dense_off),
             "dense_bytes": lay.dense_bytes, "pair_base": list(lay.pair_base), "pair_bytes": lay.pair_bytes, "feature_scale": lay.feature_scale,
             "table_bytes": lay.table_bytes, "handle_bytes": lay.handle_bytes, "half_grid_bytes": lay.half_grid_bytes}
@@ -240,21 +243,22 @@ def debug_layout(model, which: int = -1) -> dict:
 
 def debug_read(model, which: int, what: int) -> Tensor:
     """Contents of the de-hashed copies (what = 0) or the x-paired tables (what = 1) as a flat fp32 tensor on the model's device."""
-    lib = model._ensure_engine()
-    lay = debug_layout(model, which)
-    nbytes = lay["dense_bytes"] if what == 0 else lay["pair_bytes"]
-    with torch.cuda.device(model.device):
+    model._engine.ensure()
+    with torch.cuda.device(model.device), model._engine.reading() as (lib, handle):
+        lay = _layout(lib, handle, which)
+        nbytes = lay["dense_bytes"] if what == 0 else lay["pair_bytes"]
         buf = torch.empty((nbytes // 4,), dtype=torch.float32, device=model.device)
-        _lib.check(lib.sn_debug_read(model._handle, which, what, buf.data_ptr(), nbytes, _lib.current_stream()), model._handle, "sn_debug_read")
+        _lib.check(lib.sn_debug_read(handle, which, what, buf.data_ptr(), nbytes, _lib.current_stream()), handle, "sn_debug_read")
         torch.cuda.synchronize(model.device)
     return buf
 
 
 def reload_env(model) -> None:
-    """Has the handle re-read the SN_* diagnostic switches of the environment (they are otherwise read at sn_create /
-    sn_finalize_weights only) -- for tests that flip one between two renders of the same model."""
-    lib = model._ensure_engine()
-    _lib.check(lib.sn_debug_reload_env(model._handle), model._handle, "sn_debug_reload_env")
+    """Has the handle re-read the SN_* diagnostic switches of the environment (they are otherwise read when the handle is created and
+    when its weights are finalized only) -- for tests that flip one between two renders of the same model."""
+    model._engine.ensure()
+    with model._engine.reading() as (lib, handle):
+        _lib.check(lib.sn_debug_reload_env(handle), handle, "sn_debug_reload_env")
 
 
 def render_with_march_stats(model, ray_bundle):
@@ -262,12 +266,12 @@ def render_with_march_stats(model, ray_bundle):
     wave-steps of the full march)}) for "K1" and, with proposal nets, "K2 level 0" / "K2 level 1".  executed < full only through the exact
     early termination of saturated waves.  A diagnostic: not thread-safe against other renders of the same model."""
     stats = torch.zeros(3, dtype=torch.int64, device=model.device)
-    model._march_stats = stats
+    model._engine.march_stats = stats
     try:
         out = model.get_outputs_for_camera_ray_bundle(ray_bundle)
         torch.cuda.synchronize(model.device)
     finally:
-        model._march_stats = None
+        model._engine.march_stats = None
     skipped = [int(x) for x in stats.tolist()]
     H, W = ray_bundle.origins.shape[:2]
     tiles = ((W + 7) // 8) * ((H + 7) // 8) if H >= 8 else ((W + 63) // 64) * H   # the kernels' tile geometry (csrc/sn_api.hip tile_geometry)

@@ -198,3 +198,34 @@ def test_model_level_lazy_normals_survive_a_bundle_that_needed_a_copy(gpu):
     model.config.normals_bin_reuse_max_mb = 0
     out = model.get_outputs_for_camera_ray_bundle(b)
     assert torch.equal(out["normals"], always)
+
+
+def test_engine_destroys_the_handle_with_the_model_and_debug_calls_go_through_ensure(gpu, monkeypatch):
+    """The handle is released the moment the model's refcount reaches zero (no model -> engine -> model cycle: the collector is off), by one
+    sn_destroy on the handle the engine held; and the debug operators, which now take the read lock, still re-upload dirty weights first."""
+    import gc
+
+    from signerf_amd import ops
+
+    model, _ = make_model(small_config(), gpu)
+    lib = _lib.load()
+    bundle = Cameras(scene.benchmark_cameras(8)[:, :3], 8.0, 8.0, 4.0, 4.0, 8, 8).to(gpu)[0].generate_rays(camera_indices=0)
+    assert float(model.get_outputs_for_camera_ray_bundle(bundle)["rgb"].std()) > 0
+    q = torch.tensor([[0.1, 0.2, 0.3], [0.5, 0.5, 0.5], [0.9, 0.05, 0.7], [0.33, 0.66, 0.99]], device=gpu)
+    layout, features, generation = ops.debug_layout(model), ops.hash_encode(model, q), model._engine.generation
+    assert float(features.abs().max()) > 0
+    model.mark_weights_dirty()
+    assert ops.debug_layout(model) == layout and model._engine.generation == generation + 1 and not model._weights_dirty
+    model.mark_weights_dirty()
+    assert torch.equal(ops.hash_encode(model, q), features) and model._engine.generation == generation + 2
+    held, destroyed, real = model._engine.handle.value, [], lib.sn_destroy
+    assert held
+    monkeypatch.setattr(lib, "sn_destroy", lambda h: (destroyed.append(h.value), real(h))[1], raising=False)
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        del model
+        assert destroyed == [held]
+    finally:
+        if was_enabled:
+            gc.enable()

@@ -57,8 +57,8 @@ flat = bundle
 from signerf_amd import _lib  # noqa: E402
 
 S = cfg.num_nerf_samples_per_ray
-colour = timed(lambda: model._render(flat, H, W))
-eff = _lib.load().sn_effective_precision(model._handle, 1, 1)
+colour = timed(lambda: model._engine.render(flat, H, W))
+eff = _lib.load().sn_effective_precision(model._engine.handle, 1, 1)
 line = f"{a.workload} {W}x{H}x{S}, tables x{a.table_scale:g}: colour render {colour:.2f} ms"
 for prec in ("fp16x2", "fp32"):
     model.config.precision = prec
@@ -68,10 +68,10 @@ if cfg.num_proposal_iterations > 0:   # r05: the normals launch re-uses the fina
     model.config.precision = "fp16x2"
 
     def both():
-        _, st = model._render_ex(flat, H, W, keep_state=True)
+        _, st = model._engine.render(flat, H, W, keep_state=True)
         model._render_normals(flat, H, W, st)
 
     t_both = timed(both)
-    t_sep = timed(lambda: (model._render(flat, H, W), model._render_normals(flat, H, W)))
+    t_sep = timed(lambda: (model._engine.render(flat, H, W), model._render_normals(flat, H, W)))
     line += f"; colour + normals of one frame (fp16x2): {t_both:.2f} ms with the colour render's bins re-used, {t_sep:.2f} ms with the proposal sampler run twice"
 print(line + f"; a split-precision request resolves to {'fp16x2' if eff == 1 else 'EXACT FP32 (fallback)'} for the normals kernel")
