@@ -11,10 +11,24 @@
  * (the nn.Linear's own layout) and b_i = biases[i-1] [dims[i]]; h_i = relu(z_i) for i < n_layers; y = z_n [N, dims[n]].  All tensors are
  * dense fp32 DEVICE memory, aligned to 4 bytes.  1 <= n_layers <= SN_MLP_MAX_LAYERS and 1 <= dims[i] <= SN_MLP_MAX_DIM.
  *
- * Arithmetic: exact fp32 (the f32 matrix instruction, an fmaf chain; no reduced-precision operand).  A layer's output is a chain from 0
+ * Arithmetic, SnMlpDesc.precision = SN_MLP_PRECISION_FP32 (0, what a zeroed descriptor asks for): exact fp32 (the f32 matrix instruction, an fmaf chain; no reduced-precision operand).  A layer's output is a chain from 0
  * over its inputs in the order k = 16 t + 4 h + s (t = 0.., s = 0..3, h = 0..3 innermost) with the bias added LAST.  relu(NaN) is NaN, as in
  * torch; the backward mask is torch's: dZ_i = 0 where h_i <= 0, dH_i elsewhere (a NaN activation passes its gradient).  A non-finite value
  * in one row of x stays in that row of y and dx; it reaches the weight gradients, which sum over the rows.
+ *
+ * Arithmetic, SnMlpDesc.precision = SN_MLP_PRECISION_FP16 (1): the method's mixed precision -- fp16 operands, fp32 accumulation, fp32 master
+ * weights (DESIGN.md section 4 "Mixed-precision MLP").  All pointers stay fp32 device memory and the workspace has the same size.  With r16 =
+ * round-to-nearest-even to IEEE fp16 (overflow gives +-inf, subnormal results and subnormal operands are kept, NaN stays NaN):
+ * h_0 = r16(x); z_i = sum_k r16(W_i)[o][k] h_{i-1}[k] accumulated in fp32, then + b_i[o] in fp32 (the bias is added last and never rounded);
+ * h_i = r16(relu(z_i)); y = z_n in fp32.  Backward: the h_i are recomputed, bit for bit the forward's; dZ_n = r16(grad_y);
+ * dH_{i-1} = r16(W_i)^T dZ_i in fp32; dZ_{i-1} = r16(dH_{i-1}) where h_{i-1} is not <= 0 (the mask on the ROUNDED activation), else 0;
+ * grad_x = dH_0 in fp32; dW_i = sum over the points of dZ_i (x) h_{i-1} (every product exact in fp32, summed in fp32 per workgroup and in
+ * fp64 over the workgroups); db_i = sum of dZ_i in fp64.  The weights are converted from the caller's fp32 copy inside the kernels, on
+ * every call.  The order of the terms inside one 32-wide block of a sum is the matrix instruction's; the blocks are added in index order.
+ * A grad_y beyond fp16's range (a loss scale that is too large) becomes inf and reaches the gradients: the caller's grad scaler sees it.
+ * Any other value of precision is SN_ERR_INVALID from sn_mlp_forward and sn_mlp_backward (sn_mlp_backward_workspace_bytes answers 0).
+ * A library built before the field existed IGNORES it (it was `reserved`, read by no code) and computes in fp32; SN_MLP_ABI_VERSION cannot
+ * tell the two apart, because no signature and no layout changed.  sn_train_normals_analytic ignores the field: it reads the weights in fp32.
  *
  * N >= 0; N == 0 returns SN_OK without a launch and without looking at the data pointers.  A NULL or unknown-size descriptor, n_layers or a
  * dimension outside its range, N < 0, N >= 2^31, a NULL required pointer and a workspace that is too small are SN_ERR_INVALID before the
@@ -35,13 +49,15 @@ extern "C" {
 #define SN_MLP_ABI_VERSION 1
 #define SN_MLP_MAX_LAYERS 4
 #define SN_MLP_MAX_DIM 64
+#define SN_MLP_PRECISION_FP32 0
+#define SN_MLP_PRECISION_FP16 1
 int sn_mlp_abi_version(void);
 
 typedef struct SnMlpDesc {
     uint32_t struct_size;                    /* sizeof(SnMlpDesc) as the caller compiled it */
     int32_t n_layers;
     int32_t dims[SN_MLP_MAX_LAYERS + 1];     /* dims[0] = input width ... dims[n_layers] = output width */
-    int32_t reserved;                        /* 0 */
+    int32_t precision;                       /* SN_MLP_PRECISION_FP32 (0) or SN_MLP_PRECISION_FP16; the slot was `reserved`, 0, before */
     const float* weights[SN_MLP_MAX_LAYERS]; /* DEVICE [dims[i+1], dims[i]], the first n_layers are read */
     const float* biases[SN_MLP_MAX_LAYERS];  /* DEVICE [dims[i+1]] */
     /* sn_mlp_backward only: all of the first n_layers entries of BOTH arrays set, or all of them NULL (no weight gradients) */

@@ -15,6 +15,7 @@ SN_MAX_PROPOSALS = 2
 SN_OK, SN_ERR_INVALID, SN_ERR_HIP, SN_ERR_STATE, SN_ERR_WORKSPACE = 0, 1, 2, 3, 4
 SN_ABI_VERSION = 6   # include/signerf_hip.h "ABI evolution": load() refuses a library built with another one
 SN_MLP_MAX_LAYERS, SN_MLP_MAX_DIM = 4, 64
+SN_MLP_PRECISION_FP32, SN_MLP_PRECISION_FP16 = 0, 1
 SN_ADAM_MAX_TENSORS = 32
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -405,7 +406,7 @@ class SnMlpDesc(_Sized):
         ("struct_size", C.c_uint32),
         ("n_layers", C.c_int32),
         ("dims", C.c_int32 * (SN_MLP_MAX_LAYERS + 1)),
-        ("reserved", C.c_int32),
+        ("precision", C.c_int32),      # SN_MLP_PRECISION_FP32 / _FP16 (the slot "reserved" had: same offset, same size)
         ("weights", C.c_void_p * SN_MLP_MAX_LAYERS),
         ("biases", C.c_void_p * SN_MLP_MAX_LAYERS),
         ("grad_weights", C.c_void_p * SN_MLP_MAX_LAYERS),

@@ -110,6 +110,13 @@ class NerfactoModelConfig(InstantiateConfig):
     stack) run where they are called as modules, i.e. in the training forward: "torch" -- a GEMM, a bias and a ReLU per layer, as before --
     or "hip": one fused HIP kernel per pass on the exact-fp32 matrix instruction (``signerf_amd.mlp``), which keeps no hidden activation
     for the backward pass.  Default-width, torch-path fields only.  The eval render does not go through ``MLP.forward`` and is not affected."""
+    training_mlp_precision: str = "fp32"
+    """Arithmetic of the stacks ``training_mlp="hip"`` switches: "fp32" -- exact fp32, as before -- or "fp16": the method's mixed precision
+    (the reference's trainer configs set ``mixed_precision=True``), fp16 operands with fp32 accumulation on the half-precision matrix
+    instruction and the fp32 parameters as master weights (``signerf_amd.mlp``; DESIGN.md §4 "Mixed-precision MLP").  Needs
+    ``training_mlp="hip"``; pair it with ``Trainer(mixed_precision=True)``, whose grad scaler keeps the fp16 gradients in range.  Parameters,
+    state-dict keys and the eval render are the same either way, and the analytic normals of ``training_normals`` (constants for autograd)
+    keep reading the fp32 weights in fp32."""
     training_normals: bool = False
     """The normals half of a training step (``signerf_amd.train_normals``).  ``NerfactoField.forward_training(compute_normals=True)`` then
     returns per-sample analytic normals (HIP, no gradient: nerfstudio's ``Field.get_normals`` takes the density gradient without

@@ -47,6 +47,7 @@
 #include "sn_hashgrid.h"
 #include "sn_sampler.h"
 #include "sn_mlp.h"
+#include "sn_mlp_half.h"
 #include "sn_train_normals.h"
 #include "sn_normal_losses.h"
 #include "sn_optim.h"

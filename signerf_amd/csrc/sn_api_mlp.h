@@ -2,6 +2,7 @@
 #pragma once
 
 static_assert(SN_MLP_MAX_LAYERS == SN_MLP_LAYERS && SN_MLP_MAX_DIM == 16 * SN_MLP_TILES, "the header's limits are the kernels' tile counts");
+static_assert(2 * SN_MLP_HALF_KBLOCKS == SN_MLP_TILES && offsetof(SnMlpDesc, precision) == 28, "precision sits in the slot `reserved` had");
 static_assert(sizeof(SnMlpDesc) == 32 + 4 * SN_MLP_MAX_LAYERS * sizeof(void*), "SnMlpDesc has no padding the binding does not know");
 
 namespace {
@@ -21,6 +22,13 @@ int check_mlp_desc(const std::string& who, const SnMlpDesc* d, SnMlpParams& p) {
     p.n_layers = d->n_layers;
     for (int i = 0; i <= d->n_layers; ++i) p.dims[i] = d->dims[i];
     for (int i = 0; i < d->n_layers; ++i) p.image += d->dims[i + 1] * d->dims[i] + d->dims[i + 1];
+    return SN_OK;
+}
+
+// SnMlpDesc.precision (the field a library built before it existed ignored as `reserved`): one of the two arithmetics, or a refusal
+int check_mlp_precision(const std::string& who, const SnMlpDesc* d) {
+    if (d->precision != SN_MLP_PRECISION_FP32 && d->precision != SN_MLP_PRECISION_FP16)
+        return fail(nullptr, SN_ERR_INVALID, who + ": SnMlpDesc.precision " + std::to_string(d->precision) + " is neither SN_MLP_PRECISION_FP32 (0) nor SN_MLP_PRECISION_FP16 (1)");
     return SN_OK;
 }
 
@@ -58,18 +66,21 @@ int sn_mlp_forward(const SnMlpDesc* desc, const float* x, int64_t N, float* y, S
     SnMlpParams p;
     bool launch;
     if (int rc = check_mlp_desc(who, desc, p)) return rc;
+    if (int rc = check_mlp_precision(who, desc)) return rc;
     if (int rc = check_mlp_call(who, desc, N, x && y, "x, y", p, &launch)) return rc;
     if (!launch) return SN_OK;
     if (((uintptr_t)x | (uintptr_t)y) & 3) return fail(nullptr, SN_ERR_INVALID, who + ": x and y must be aligned to 4 bytes");
     p.x = x;
     p.y = y;
-    hipLaunchKernelGGL(sn_train_mlp_forward_kernel, blocks_for(N, SN_MLP_WG_POINTS), dim3(SN_MLP_BLOCK), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(desc->precision == SN_MLP_PRECISION_FP16 ? sn_train_mlp_half_forward_kernel : sn_train_mlp_forward_kernel,
+                       blocks_for(N, SN_MLP_WG_POINTS), dim3(SN_MLP_BLOCK), 0, (hipStream_t)stream, p);
     return end_launches(who);
 }
 
 size_t sn_mlp_backward_workspace_bytes(const SnMlpDesc* desc, int64_t N) {
     SnMlpParams p;
-    if (check_mlp_desc("sn_mlp_backward_workspace_bytes", desc, p) != SN_OK || N <= 0 || N > 0x7fffffffll) return 0;
+    const std::string who = "sn_mlp_backward_workspace_bytes";
+    if (check_mlp_desc(who, desc, p) != SN_OK || check_mlp_precision(who, desc) != SN_OK || N <= 0 || N > 0x7fffffffll) return 0;
     return (size_t)mlp_partials(N) * (size_t)p.image * sizeof(float);
 }
 
@@ -79,6 +90,7 @@ int sn_mlp_backward(const SnMlpDesc* desc, const float* x, const float* grad_y, 
     SnMlpParams p;
     bool launch;
     if (int rc = check_mlp_desc(who, desc, p)) return rc;
+    if (int rc = check_mlp_precision(who, desc)) return rc;
     int n_grads = 0;
     for (int i = 0; i < desc->n_layers; ++i) n_grads += (desc->grad_weights[i] ? 1 : 0) + (desc->grad_biases[i] ? 1 : 0);
     if (n_grads != 0 && n_grads != 2 * desc->n_layers)
@@ -104,7 +116,8 @@ int sn_mlp_backward(const SnMlpDesc* desc, const float* x, const float* grad_y, 
         }
         p.partials = (float*)workspace;
     }
-    hipLaunchKernelGGL(sn_train_mlp_backward_kernel, dim3((unsigned)p.n_partials), dim3(SN_MLP_BLOCK), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(desc->precision == SN_MLP_PRECISION_FP16 ? sn_train_mlp_half_backward_kernel : sn_train_mlp_backward_kernel,
+                       dim3((unsigned)p.n_partials), dim3(SN_MLP_BLOCK), 0, (hipStream_t)stream, p);
     if (n_grads) hipLaunchKernelGGL(sn_train_mlp_reduce_kernel, blocks_for(p.image, SN_MLP_BLOCK), dim3(SN_MLP_BLOCK), 0, (hipStream_t)stream, p);
     return end_launches(who);
 }

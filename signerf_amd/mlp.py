@@ -4,7 +4,10 @@
 
 As torch ops every layer is a GEMM, a bias and a ReLU that writes and re-reads an ``[N, width]`` activation, the same again backwards, and
 every hidden activation stays alive for autograd.  Here the forward pass keeps nothing but its input, and the backward pass recomputes the
-hidden activations of each tile of points (DESIGN.md §4 "Trainable MLP").  The arithmetic is exact fp32 (the f32 matrix instruction).
+hidden activations of each tile of points (DESIGN.md §4 "Trainable MLP").  The arithmetic is exact fp32 (the f32 matrix instruction) with
+``precision="fp32"``, the default, and the method's mixed precision with ``precision="fp16"``: fp16 operands, fp32 accumulation, fp32 master
+weights, rounded where include/signerf_hip_mlp.h says (DESIGN.md §4 "Mixed-precision MLP"; csrc/sn_mlp_half.h).  The tensors are fp32 under
+both: the kernels round ``x``, the weights and the incoming gradient themselves, and a gradient beyond fp16's range becomes inf there.
 
 Inputs are fp32 GPU tensors: another dtype raises ``TypeError``, a CPU tensor raises ``SignerfHipError`` (there is no CPU path), a
 non-contiguous tensor is made contiguous (a contiguous view into the middle of a storage is taken as it is: the entry points ask for 4-byte
@@ -28,6 +31,7 @@ from . import _lib
 MAX_LAYERS, MAX_DIM = _lib.SN_MLP_MAX_LAYERS, _lib.SN_MLP_MAX_DIM
 # (the kernels move single fp32 elements: any fp32 tensor's 4-byte alignment is all the entry points ask for)
 TAKES = "the MLP kernels take fp32 points and fp32 weights"
+PRECISIONS = {"fp32": _lib.SN_MLP_PRECISION_FP32, "fp16": _lib.SN_MLP_PRECISION_FP16}   # SnMlpDesc.precision
 WG_POINTS, MAX_PARTIALS = 64, 256   # csrc/sn_mlp.h: the backward kernel's point tile and its cap on partial gradient images
 
 
@@ -36,6 +40,13 @@ def check_dims(dims: Sequence[int]) -> None:
     if not 1 <= len(dims) - 1 <= MAX_LAYERS or not all(1 <= int(d) <= MAX_DIM for d in dims):
         raise ValueError(f"fused_mlp: 1..{MAX_LAYERS} layers with every width in 1..{MAX_DIM} expected, got dims {tuple(dims)} "
                          "(wide, 128-unit fields are not built for the HIP MLP)")
+
+
+def check_precision(precision) -> int:
+    """-> SnMlpDesc.precision; raises ValueError for anything but "fp32" and "fp16"."""
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"fused_mlp: precision={precision!r}: one of {sorted(PRECISIONS)} expected")
+    return PRECISIONS[precision]
 
 
 def partials(N: int) -> int:
@@ -48,9 +59,9 @@ def workspace_floats(dims: Sequence[int], N: int) -> int:
     return partials(N) * sum(dims[i + 1] * dims[i] + dims[i + 1] for i in range(len(dims) - 1))
 
 
-def _desc(dims, weights, biases, grad_weights=None, grad_biases=None) -> _lib.SnMlpDesc:
+def _desc(dims, weights, biases, grad_weights=None, grad_biases=None, precision: int = 0) -> _lib.SnMlpDesc:
     d = _lib.SnMlpDesc()
-    d.n_layers = len(weights)
+    d.n_layers, d.precision = len(weights), precision
     for i, v in enumerate(dims):
         d.dims[i] = v
     for i in range(len(weights)):
@@ -60,17 +71,17 @@ def _desc(dims, weights, biases, grad_weights=None, grad_biases=None) -> _lib.Sn
     return d
 
 
-def _forward(x: Tensor, dims, weights, biases) -> Tensor:
+def _forward(x: Tensor, dims, weights, biases, precision: int = 0) -> Tensor:
     N = x.shape[0]
     with torch.cuda.device(x.device):
         y = torch.empty((N, dims[-1]), dtype=torch.float32, device=x.device)
         if N > 0:
-            _lib.check(_lib.load().sn_mlp_forward(C.byref(_desc(dims, weights, biases)), _lib.ptr(x), N, _lib.ptr(y), _lib.current_stream()),
-                       None, "sn_mlp_forward")
+            _lib.check(_lib.load().sn_mlp_forward(C.byref(_desc(dims, weights, biases, precision=precision)), _lib.ptr(x), N, _lib.ptr(y),
+                                                  _lib.current_stream()), None, "sn_mlp_forward")
     return y
 
 
-def _backward(x: Tensor, g: Tensor, dims, weights, biases, want_x: bool, want_w: bool):
+def _backward(x: Tensor, g: Tensor, dims, weights, biases, want_x: bool, want_w: bool, precision: int = 0):
     """-> (grad_x or None, [grad_W...] or None, [grad_b...] or None); the workspace comes from torch's allocator."""
     N = x.shape[0]
     with torch.cuda.device(x.device):
@@ -82,35 +93,37 @@ def _backward(x: Tensor, g: Tensor, dims, weights, biases, want_x: bool, want_w:
                 t.zero_()
             return g_x, g_w, g_b
         ws = torch.empty(workspace_floats(dims, N), dtype=torch.float32, device=x.device) if want_w else None
-        _lib.check(_lib.load().sn_mlp_backward(C.byref(_desc(dims, weights, biases, g_w, g_b)), _lib.ptr(x), _lib.ptr(g), N, _lib.ptr(g_x),
-                                               _lib.ptr(ws), 4 * ws.numel() if ws is not None else 0, _lib.current_stream()),
+        _lib.check(_lib.load().sn_mlp_backward(C.byref(_desc(dims, weights, biases, g_w, g_b, precision)), _lib.ptr(x), _lib.ptr(g), N,
+                                               _lib.ptr(g_x), _lib.ptr(ws), 4 * ws.numel() if ws is not None else 0, _lib.current_stream()),
                    None, "sn_mlp_backward")
     return g_x, g_w, g_b
 
 
 class _FusedMLP(torch.autograd.Function):
-    """(x [N, d_0], W_1, b_1, ..., W_n, b_n) -> y [N, d_n]."""
+    """(precision, x [N, d_0], W_1, b_1, ..., W_n, b_n) -> y [N, d_n]; precision: SnMlpDesc's, not differentiable."""
 
     @staticmethod
-    def forward(ctx, x, *params):
+    def forward(ctx, precision, x, *params):
         weights, biases = params[0::2], params[1::2]
+        ctx.precision = precision
         ctx.dims = [x.shape[1]] + [w.shape[0] for w in weights]
         ctx.save_for_backward(x, *params)   # the backward pass recomputes the hidden activations from x
-        return _forward(x, ctx.dims, weights, biases)
+        return _forward(x, ctx.dims, weights, biases, precision)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
         x, *params = ctx.saved_tensors
         weights, biases = params[0::2], params[1::2]
-        want_x, want_w = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:])
+        needs = ctx.needs_input_grad[1:]   # (of x and the parameters)
+        want_x, want_w = needs[0], any(needs[1:])
         if not (want_x or want_w):
-            return (None,) * (1 + len(params))
+            return (None,) * (2 + len(params))
         g = _lib.prep(g.to(torch.float32), "grad_y", TAKES)
-        g_x, g_w, g_b = _backward(x, g, ctx.dims, weights, biases, want_x, want_w)
-        out = [g_x]
+        g_x, g_w, g_b = _backward(x, g, ctx.dims, weights, biases, want_x, want_w, ctx.precision)
+        out = [None, g_x]
         for i in range(len(weights)):
-            out += [g_w[i] if want_w and ctx.needs_input_grad[1 + 2 * i] else None, g_b[i] if want_w and ctx.needs_input_grad[2 + 2 * i] else None]
+            out += [g_w[i] if want_w and needs[1 + 2 * i] else None, g_b[i] if want_w and needs[2 + 2 * i] else None]
         return tuple(out)
 
 
@@ -138,26 +151,30 @@ def _check(x, weights, biases):
     return x, weights, biases, dims
 
 
-def fused_mlp(x: Tensor, weights: Sequence[Tensor], biases: Sequence[Tensor]) -> Tensor:
+def fused_mlp(x: Tensor, weights: Sequence[Tensor], biases: Sequence[Tensor], precision: str = "fp32") -> Tensor:
     """``x [..., d_0]`` through the layers ``weights[i] [d_{i+1}, d_i]``, ``biases[i] [d_{i+1}]`` (an ``nn.Linear``'s ``weight`` and
     ``bias``) with a ReLU between layers and none after the last -> ``[..., d_n]``.  Differentiable once, in ``x`` and in every parameter
-    that requires a gradient."""
+    that requires a gradient.  ``precision``: "fp32", exact fp32, or "fp16", fp16 operands with fp32 accumulation (the module docstring)."""
+    precision = check_precision(precision)
     x, weights, biases, dims = _check(x, weights, biases)
     lead = x.shape[:-1]
     params = [t for pair in zip(weights, biases) for t in pair]
-    y = _FusedMLP.apply(x.reshape(-1, dims[0]), *params)
+    y = _FusedMLP.apply(precision, x.reshape(-1, dims[0]), *params)
     return y.reshape(*lead, dims[-1])
 
 
-def mlp_forward(x: Tensor, weights: Sequence[Tensor], biases: Sequence[Tensor]) -> Tensor:
+def mlp_forward(x: Tensor, weights: Sequence[Tensor], biases: Sequence[Tensor], precision: str = "fp32") -> Tensor:
     """The forward entry point as it is, no autograd graph: for tests and measurements."""
+    precision = check_precision(precision)
     x, weights, biases, dims = _check(x, weights, biases)
-    return _forward(x.detach().reshape(-1, dims[0]), dims, [w.detach() for w in weights], [b.detach() for b in biases]).reshape(*x.shape[:-1], dims[-1])
+    return _forward(x.detach().reshape(-1, dims[0]), dims, [w.detach() for w in weights], [b.detach() for b in biases],
+                    precision).reshape(*x.shape[:-1], dims[-1])
 
 
 def mlp_backward(x: Tensor, weights: Sequence[Tensor], biases: Sequence[Tensor], grad_y: Tensor, want_grad_x: bool = True,
-                 want_grad_params: bool = True):
+                 want_grad_params: bool = True, precision: str = "fp32"):
     """The backward entry point as it is, for tests and measurements -> (grad_x or None, [grad_W...] or None, [grad_b...] or None)."""
+    precision = check_precision(precision)
     x, weights, biases, dims = _check(x, weights, biases)
     grad_y = _lib.prep(grad_y, "grad_y", TAKES).detach()
     N = x.numel() // dims[0]
@@ -166,5 +183,5 @@ def mlp_backward(x: Tensor, weights: Sequence[Tensor], biases: Sequence[Tensor],
     if not (want_grad_x or want_grad_params):
         raise ValueError("mlp_backward: want_grad_x or want_grad_params expected")
     g_x, g_w, g_b = _backward(x.detach().reshape(-1, dims[0]), grad_y.reshape(-1, dims[-1]), dims, [w.detach() for w in weights],
-                              [b.detach() for b in biases], want_grad_x, want_grad_params)
+                              [b.detach() for b in biases], want_grad_x, want_grad_params, precision)
     return (g_x.reshape(x.shape) if g_x is not None else None), g_w, g_b

@@ -94,9 +94,11 @@ class HashEncoding(nn.Module):
 class MLP(nn.Module):
     """Parameters of nerfstudio's torch MLP: ``layers`` = nn.Linear list (A8).  ``implementation``: "torch" -- ``forward`` is the torch ops
     below -- or "hip": the same parameters through ``mlp.fused_mlp`` (one HIP kernel per pass; GPU tensors, at most 4 layers of at most 64
-    units).  A plain attribute, not state: the state dict is the same either way."""
+    units).  ``precision``: "fp32", or "fp16" -- the fused op's mixed precision (fp16 operands, fp32 accumulation, these fp32 parameters as
+    the master copy), which exists for "hip" alone.  Plain attributes, not state: the state dict is the same either way."""
 
     implementation = "torch"   # (class-level: a module pickled whole before the attribute existed still runs the torch ops)
+    precision = "fp32"         # (class-level, for the same reason)
 
     def __init__(self, in_dim: int, num_layers: int, layer_width: int, out_dim: int, implementation: str = "torch"):
         super().__init__()
@@ -107,9 +109,12 @@ class MLP(nn.Module):
     def forward(self, in_tensor: Tensor) -> Tensor:
         """The ``nn.Linear`` stack with a ReLU between layers and no output activation (torch ops; ``oracle.nerfacto.mlp_forward``)."""
         if self.implementation == "hip":
-            return mlp.fused_mlp(in_tensor, [layer.weight for layer in self.layers], [layer.bias for layer in self.layers])
+            return mlp.fused_mlp(in_tensor, [layer.weight for layer in self.layers], [layer.bias for layer in self.layers], self.precision)
         if self.implementation != "torch":
             raise ValueError(f'MLP.implementation={self.implementation!r}: "torch" or "hip" expected')
+        if self.precision != "fp32":
+            raise ValueError(f'MLP.precision={self.precision!r} with implementation="torch": the torch path is fp32 here; the mixed-precision '
+                             'arithmetic is the fused HIP op\'s and needs implementation="hip"')
         x = in_tensor
         for i, layer in enumerate(self.layers):
             x = layer(x)
@@ -562,6 +567,10 @@ class NerfactoModel(nn.Module):
         self.density_fns = [net.density_fn for net in self.proposal_networks]   # nerfstudio's NerfactoModel attribute [NS-RECALL, H]
         if cfg.training_mlp not in TRAINING_MLPS:
             raise ValueError(f"training_mlp={cfg.training_mlp!r}: one of {sorted(TRAINING_MLPS)} expected")
+        mlp.check_precision(cfg.training_mlp_precision)
+        if cfg.training_mlp_precision != "fp32" and cfg.training_mlp != "hip":
+            raise NotImplementedError(f'training_mlp_precision={cfg.training_mlp_precision!r} with training_mlp={cfg.training_mlp!r}: the '
+                                      'mixed-precision arithmetic is the fused HIP MLP\'s; it needs training_mlp="hip" (the torch stacks are fp32)')
         if cfg.training_mlp == "hip":
             if cfg.implementation != "torch":
                 raise NotImplementedError(f'training_mlp="hip" with implementation={cfg.implementation!r}: the HIP MLP reads the nn.Linear '
@@ -574,7 +583,7 @@ class NerfactoModel(nn.Module):
                     mlp.check_dims([stack.layers[0].in_features] + [layer.out_features for layer in stack.layers])
                 except ValueError as e:
                     raise NotImplementedError(f'training_mlp="hip": {e}; wide fields train with training_mlp="torch"') from None
-                stack.implementation = "hip"
+                stack.implementation, stack.precision = "hip", cfg.training_mlp_precision
         self.camera_optimizer = CameraOptimizer(self.num_train_data, cfg.camera_optimizer_mode)
 
     @property

@@ -5,8 +5,12 @@ is not viewer or dataset generation: one training iteration over ``Optimizers``,
     for step in range(trainer._start_step, n):
         loss, loss_dict, metrics_dict = trainer.train_iteration(step)
 
-The grad scaler exists and is checkpointed, as nerfstudio's ``GradScaler(enabled=mixed_precision)``; mixed-precision ARITHMETIC is not built
-(the forward pass is fp32 under either setting), so with ``mixed_precision=True`` the scaler scales and unscales fp32 gradients.
+The grad scaler is nerfstudio's ``GradScaler(enabled=mixed_precision)`` and is checkpointed.  ``mixed_precision=True`` together with a model
+built with ``training_mlp="hip", training_mlp_precision="fp16"`` is the reference's configuration: the ``nn.Linear`` stacks then compute on
+fp16 operands with fp32 accumulation (``signerf_amd.mlp``).  The scaler's factor reaches those kernels through the incoming gradient ``g``,
+which they round to fp16; where the scaled ``g`` leaves fp16's range, ``r16(g)`` is inf, the inf reaches the parameter gradients, the
+optimiser's found-inf path skips the step and ``update()`` halves the scale.  With the model's default ``training_mlp_precision="fp32"`` the
+forward pass is fp32 and the scaler scales and unscales fp32 gradients.
 """
 
 from __future__ import annotations

@@ -7,7 +7,12 @@ Stacks at the sizes of a nerfacto step at 4096 rays with (256, 96, 48) samples p
 and parameter gradients), the median of 50 hipEvent spans after a warm-up.  Then one whole training step of the default model (4096 rays,
 ``get_training_outputs`` -> ``get_loss_dict`` -> ``backward()``) with ``training_mlp`` set each way.
 
+``--precision fp16`` measures the mixed-precision arithmetic instead (DESIGN.md §4 "Mixed-precision MLP"): the same four stacks and the same
+whole step on the HIP MLP with ``precision`` "fp32" and "fp16", in the same process -- the base of every fp16 figure is the fp32 figure of
+the same run -- written to profiles/mlp_bench_half.json.
+
     python tools/mlp_bench.py [--reps 50] [--out profiles/mlp_bench.json]
+    python tools/mlp_bench.py --precision fp16 [--out profiles/mlp_bench_half.json]
 """
 import argparse
 import json
@@ -28,8 +33,14 @@ ap.add_argument("--rays", type=int, default=4096)
 ap.add_argument("--reps", type=int, default=50)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--no-step", action="store_true")
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mlp_bench.json"))
+ap.add_argument("--precision", choices=("fp32", "fp16"), default="fp32", help="fp16: time the HIP MLP in fp32 and in fp16 instead of hip against torch")
+ap.add_argument("--out", default=None, help="default: profiles/mlp_bench.json, or profiles/mlp_bench_half.json with --precision fp16")
 a = ap.parse_args()
+HALF = a.precision == "fp16"
+a.out = a.out or os.path.join(ROOT, "profiles", "mlp_bench_half.json" if HALF else "mlp_bench.json")
+# (label, MLP.implementation / training_mlp, MLP.precision / training_mlp_precision) of the two sides; the ratio is second over first
+SIDES = [("fp16", "hip", "fp16"), ("fp32", "hip", "fp32")] if HALF else [("hip", "hip", "fp32"), ("torch", "torch", "fp32")]
+RATIO = SIDES[1][0] + "_over_" + SIDES[0][0]
 dev = torch.device("cuda", 0)
 STACKS = {"main_base": (48, (32, 64, 16)), "main_head": (48, (63, 64, 64, 3)), "proposal_0": (256, (10, 16, 1)), "proposal_1": (96, (10, 16, 1))}
 
@@ -68,11 +79,11 @@ for name, (samples, dims) in STACKS.items():
             net(x)
 
     rec = {"points": N, "dims": list(dims)}
-    for impl in ("hip", "torch"):
-        net.implementation = impl
-        rec[impl] = span(step)
-        rec[impl + "_forward"] = span(forward)
-    rec["torch_over_hip"] = round(rec["torch"]["ms_median"] / rec["hip"]["ms_median"], 2)
+    for label, impl, precision in SIDES:
+        net.implementation, net.precision = impl, precision
+        rec[label] = span(step)
+        rec[label + "_forward"] = span(forward)
+    rec[RATIO] = round(rec[SIDES[1][0]]["ms_median"] / rec[SIDES[0][0]]["ms_median"], 2)
     results[name] = rec
     print(name, json.dumps(rec), flush=True)
     del net, x, g
@@ -87,9 +98,10 @@ if not a.no_step:
     bundle = RayBundle(origins=o.to(dev), directions=torch.nn.functional.normalize(look - o, dim=-1).to(dev), pixel_area=torch.ones(R, 1, device=dev),
                        camera_indices=torch.randint(0, 4, (R, 1), generator=gen).to(dev))
     batch = {"image": torch.rand(R, 3, generator=gen).to(dev)}
-    for impl in ("hip", "torch"):
+    for label, impl, precision in SIDES:
         torch.manual_seed(0)
-        model = NerfactoModelConfig(training_forward=True, training_mlp=impl, num_train_data=4, camera_optimizer_mode="off").setup().to(dev)
+        model = NerfactoModelConfig(training_forward=True, training_mlp=impl, training_mlp_precision=precision, num_train_data=4,
+                                    camera_optimizer_mode="off").setup().to(dev)
         model.train()
         at = [0]
 
@@ -100,16 +112,17 @@ if not a.no_step:
             out = model(bundle)
             sum(model.get_loss_dict(out, batch, model.get_metrics_dict(out, batch)).values()).backward()
 
-        step_rec[impl] = span(train_step)
-        print("training_step", impl, json.dumps(step_rec[impl]), flush=True)
+        step_rec[label] = span(train_step)
+        print("training_step", label, json.dumps(step_rec[label]), flush=True)
         del model
         torch.cuda.empty_cache()
-    step_rec["torch_over_hip"] = round(step_rec["torch"]["ms_median"] / step_rec["hip"]["ms_median"], 2)
+    step_rec[RATIO] = round(step_rec[SIDES[1][0]]["ms_median"] / step_rec[SIDES[0][0]]["ms_median"], 2)
 
-doc = {"tool": "tools/mlp_bench.py", "device": torch.cuda.get_device_name(0), "rays": a.rays, "reps": a.reps,
-       "note": "forward + backward (input and parameter gradients) per call, ms, median of hipEvent spans; `torch`: the same MLP module on "
-               "implementation=\"torch\" (nn.Linear + relu with autograd) on the same GPU in the same process; `training_step`: the default "
-               "nerfacto, 4096 rays, levels (256, 96, 48), forward + losses + backward, no optimiser",
+other = ("`fp32` / `fp16`: the MLP module on implementation=\"hip\" with that precision, same GPU, same process" if HALF else
+         "`torch`: the same MLP module on implementation=\"torch\" (nn.Linear + relu with autograd) on the same GPU in the same process")
+doc = {"tool": "tools/mlp_bench.py" + (" --precision fp16" if HALF else ""), "device": torch.cuda.get_device_name(0), "rays": a.rays, "reps": a.reps,
+       "note": "forward + backward (input and parameter gradients) per call, ms, median of hipEvent spans; " + other + "; `training_step`: the "
+               "default nerfacto, 4096 rays, levels (256, 96, 48), forward + losses + backward, no optimiser",
        "results": results, "training_step": step_rec}
 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
 with open(a.out, "w") as f:
