@@ -160,17 +160,25 @@ class Header(NamedTuple):
 
 
 REGISTRY: Tuple[Header, ...] = ()
+# Headers that ship with the package, under signerf_amd/include/ (EXTENSION_DIR): REGISTRY is the tree's include/, file for file
+# (tests/test_cabi.py holds the two against each other), and an extension's header stands outside both.  load() binds and version-checks
+# either kind; header(key) finds either; functions() stays REGISTRY's.  Each extension has a host test of its own.
+EXTENSIONS: Tuple[Header, ...] = ()
+EXTENSION_DIR = os.path.join(_PKG_DIR, "include")
 
 
-def _add(key: str, version: int, recorded: bool, functions: dict) -> None:
-    global REGISTRY
+def _add(key: str, version: int, recorded: bool, functions: dict, extension: bool = False) -> None:
+    global REGISTRY, EXTENSIONS
     infix = "" if key == "core" else "_" + key
-    REGISTRY += (Header(key, f"signerf_hip{infix}.h", f"sn{infix}_abi_version", f"SN{infix.upper()}_ABI_VERSION", version, functions,
-                        recorded),)
+    h = Header(key, f"signerf_hip{infix}.h", f"sn{infix}_abi_version", f"SN{infix.upper()}_ABI_VERSION", version, functions, recorded)
+    if extension:
+        EXTENSIONS += (h,)
+    else:
+        REGISTRY += (h,)
 
 
 def header(key: str) -> Header:
-    return {h.key: h for h in REGISTRY}[key]
+    return {h.key: h for h in REGISTRY + EXTENSIONS}[key]
 
 
 def functions(recorded: Optional[bool] = None) -> dict:
@@ -353,6 +361,14 @@ _add("hashgrid", version=1, recorded=False, functions={
     "sn_hashgrid_backward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p]),
 })
 
+# signerf_amd/include/signerf_hip_hashgrid_tcnn.h: the trainable tiny-cuda-nn grid (its host test: tests/test_tcnn_hashgrid_host.py)
+_add("hashgrid_tcnn", version=1, recorded=False, extension=True, functions={
+    "sn_hashgrid_tcnn_abi_version": (C.c_int, []),
+    "sn_hashgrid_tcnn_levels": (C.c_int, [C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32)]),
+    "sn_hashgrid_tcnn_forward": (C.c_int, [_FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p]),
+    "sn_hashgrid_tcnn_backward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p]),
+})
 
 
 class SnSamplerRays(_Sized):
@@ -505,14 +521,15 @@ def load() -> C.CDLL:
             lib = C.CDLL(LIB_PATH)
         except OSError as e:  # pragma: no cover
             raise SignerfHipError(f"cannot load {LIB_PATH}: {e}") from e
-        for name, (res, args) in functions().items():
+        bound = dict(functions(), **{name: sig for h in EXTENSIONS for name, sig in h.functions.items()})
+        for name, (res, args) in bound.items():
             fn = getattr(lib, name, None)
             if fn is None:
                 raise SignerfHipError(f"{LIB_PATH} does not export {name}: it was built from another include/signerf_hip.h -- rebuild it "
                                       "(`python -m signerf_amd.build --force`)")
             fn.restype = res
             fn.argtypes = args
-        for h in REGISTRY:
+        for h in REGISTRY + EXTENSIONS:
             got = getattr(lib, h.version_fn)()
             if got != h.version:
                 raise SignerfHipError(f"{LIB_PATH} reports {h.version_macro} {got}, this binding was written for {h.version}: "

@@ -21,6 +21,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libsignerf_hip.so")
 SOURCES = ["sn_api.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", h.file) for h in _lib.REGISTRY]
+HEADERS += [os.path.join("..", "include", h.file) for h in _lib.EXTENSIONS]   # (signerf_amd/include/: _lib.EXTENSION_DIR)
 ARCH = "gfx950"
 # Code-generation flags of the device code (tools/isa_hazard_scan.py compiles with the same ones).
 #   -fno-slp-vectorize, -disable-vector-combine: keep hipcc from packing neighbouring fp32 operations into v_pk_fma_f32 /

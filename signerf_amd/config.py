@@ -124,6 +124,14 @@ class NerfactoModelConfig(InstantiateConfig):
     ``predict_normals`` model adds ``normals``, ``pred_normals``, ``rendered_orientation_loss`` and ``rendered_pred_normal_loss``, so
     ``get_loss_dict`` gains ``orientation_loss`` and ``pred_normal_loss``.  Off by default: the training forward is then what it was, and
     ``forward_training(compute_normals=True)`` raises ``NotImplementedError``."""
+    training_tcnn: bool = False
+    """Makes an ``implementation="tcnn"`` model trainable: fine-tuning an imported ``ns-train nerfacto`` checkpoint, what SIGNeRF does.
+    ``HashEncoding.forward`` of its grids then runs the differentiable tiny-cuda-nn grid in HIP (``hashgrid.hash_encode(grid="tcnn")``),
+    ``get_density_training`` / ``forward_training`` / ``get_training_outputs`` work in the eval field's tcnn forms (SH on ``d``), and
+    ``training_mlp="hip"`` is accepted in both precisions: after the import the stacks are plain ``nn.Linear`` ones.  Their biases (zero, or
+    folded from the library's input padding) are ordinary parameters and train, so the result is saved in this package's state-dict
+    layout, not as tiny-cuda-nn's flat vectors.  ``training_normals`` with it raises ``NotImplementedError``.  Off by default: a tcnn model
+    then refuses every training entry point, as before.  Ignored by ``implementation="torch"``."""
     dense_levels: int = 0
     """Memory budget of the derived gather buffers the HIP library builds beside the uploaded tables (``SnFieldDesc.dense_levels``):
     0 = default (the 11 coarsest levels of the main grid get a de-hashed copy: 1.26 GB per model for nerfacto's grid, + 0.47 GB of x-paired

@@ -10,11 +10,16 @@ namespace {
 // scale 128..212 gains (a proposal level at 256 samples per ray 1.4x..1.7x each), the levels above 256 neither gain nor lose.
 constexpr float kSnHashgridMergeMaxScale = 256.0f;
 std::atomic<float> g_hashgrid_merge_max_scale{kSnHashgridMergeMaxScale};
+// the same threshold for the tiny-cuda-nn grid (sn_api_hashgrid_tcnn.h), whose scales are res - 1 and whose coarse levels are dense: the
+// sweep of tools/hashgrid_bench.py --grid tcnn (DESIGN.md §4 "Trainable tcnn grid", "A/B").  The variable overrides both.
+constexpr float kSnHashgridTcnnMergeMaxScale = 256.0f;
+std::atomic<float> g_hashgrid_tcnn_merge_max_scale{kSnHashgridTcnnMergeMaxScale};
 std::once_flag g_hashgrid_env_once;
 
 void load_hashgrid_env() {
     const char* e = getenv("SN_HASHGRID_MERGE_MAX_SCALE");
     g_hashgrid_merge_max_scale = e ? (float)atof(e) : kSnHashgridMergeMaxScale;
+    g_hashgrid_tcnn_merge_max_scale = e ? (float)atof(e) : kSnHashgridTcnnMergeMaxScale;
 }
 
 // the checks both entry points share, in this order; *launch says whether anything is left to do

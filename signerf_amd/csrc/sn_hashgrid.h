@@ -23,6 +23,11 @@
 // domain at EVERY level: NaN features, zero index rows, no contribution to grad_table, a NaN grad_q row.  Inside the domain floor and ceil
 // fit int32; the row index is masked with T - 1, so no input addresses outside the table.  Element offsets into the table are 32-bit
 // (the entry points refuse L * T * F >= 2^31).
+//
+// Cell policy.  The three kernels take a class G after F that says what a cell IS: the domain, the 8 rows and 3 offsets of a point at a
+// level, which corners take 1 - o on which axis, the forward blend and where nerfstudio's corner i sits among the 8.  SnHgTorchGrid (the
+// default) is everything above; SnHgTcnnGrid (sn_hashgrid_tcnn.h) is tiny-cuda-nn's grid.  The mapping, the merged atomics and the fp64
+// rules are shared.
 #pragma once
 #include "sn_device.h"
 
@@ -117,35 +122,14 @@ SN_DEV void sn_hg_cell(const float q[3], float s, int l, int log2_T, uint32_t ro
         row[k] = ((h[0][(SN_HG_XF >> k) & 1u] ^ h[1][(SN_HG_YF >> k) & 1u] ^ h[2][(SN_HG_ZF >> k) & 1u]) & mask) + base;
 }
 
-template <int F>
-__global__ __launch_bounds__(SN_HG_BLOCK) void sn_hashgrid_forward_kernel(SnHashgridParams p) {
-    const uint64_t t = (uint64_t)blockIdx.x * SN_HG_BLOCK + threadIdx.x, total = (uint64_t)p.N * (uint32_t)p.L;
-    if (t >= total) return;
-    int64_t n;
-    if (total <= 0xffffffffull) n = (uint32_t)t / (uint32_t)p.L;   // (block-uniform: a 32-bit divide whenever the batch allows it)
-    else n = (int64_t)(t / (uint32_t)p.L);
-    const int l = (int)(t - (uint64_t)n * (uint32_t)p.L);
-    const float q[3] = {p.q[n * 3], p.q[n * 3 + 1], p.q[n * 3 + 2]};
-    float* out = p.enc + (int64_t)t * F;
-    int32_t* irow = p.idx ? p.idx + (int64_t)t * 8 : nullptr;
-    SnHgRow<F> e;
-    if (!sn_hg_in_domain(q, p.scal, p.L)) {
-#pragma unroll
-        for (int f = 0; f < F; ++f) e.v[f] = __builtin_nanf("");
-        sn_hg_store<F>(out, e);
-        if (irow) {
-            *reinterpret_cast<int4*>(irow) = make_int4(0, 0, 0, 0);
-            *reinterpret_cast<int4*>(irow + 4) = make_int4(0, 0, 0, 0);
-        }
-        return;
-    }
-    uint32_t row[8];
-    float o[3];
-    sn_hg_cell(q, p.scal[l], l, p.log2_T, row, o);
-    SnHgRow<F> c[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) c[k] = sn_hg_load<F>(p.table + row[k] * (uint32_t)F);
-    {
+// nerfstudio's torch-path grid as a cell policy: the functions above, the corner masks, nerfstudio's blend nesting in fp32
+struct SnHgTorchGrid {
+    static constexpr uint32_t XF = SN_HG_XF, YF = SN_HG_YF, ZF = SN_HG_ZF;
+    static constexpr int slot(int i) { return i; }   // where corner i of nerfstudio's order sits in row[] / c[]
+    static SN_DEV bool in_domain(const float q[3], const float* scal, int L) { return sn_hg_in_domain(q, scal, L); }
+    static SN_DEV void cell(const float q[3], float s, int l, int log2_T, uint32_t row[8], float o[3]) { sn_hg_cell(q, s, l, log2_T, row, o); }
+    template <int F>
+    static SN_DEV void blend(const SnHgRow<F> c[8], const float o[3], SnHgRow<F>& e) {
 #pragma clang fp contract(off)
         const float ox = o[0], oy = o[1], oz = o[2], rx = 1.0f - ox, ry = 1.0f - oy, rz = 1.0f - oz;
 #pragma unroll
@@ -159,6 +143,37 @@ __global__ __launch_bounds__(SN_HG_BLOCK) void sn_hashgrid_forward_kernel(SnHash
             e.v[f] = f0312 * oz + f4756 * rz;
         }
     }
+};
+
+template <int F, class G = SnHgTorchGrid>
+__global__ __launch_bounds__(SN_HG_BLOCK) void sn_hashgrid_forward_kernel(SnHashgridParams p) {
+    const uint64_t t = (uint64_t)blockIdx.x * SN_HG_BLOCK + threadIdx.x, total = (uint64_t)p.N * (uint32_t)p.L;
+    if (t >= total) return;
+    int64_t n;
+    if (total <= 0xffffffffull) n = (uint32_t)t / (uint32_t)p.L;   // (block-uniform: a 32-bit divide whenever the batch allows it)
+    else n = (int64_t)(t / (uint32_t)p.L);
+    const int l = (int)(t - (uint64_t)n * (uint32_t)p.L);
+    const float q[3] = {p.q[n * 3], p.q[n * 3 + 1], p.q[n * 3 + 2]};
+    float* out = p.enc + (int64_t)t * F;
+    int32_t* irow = p.idx ? p.idx + (int64_t)t * 8 : nullptr;
+    SnHgRow<F> e;
+    if (!G::in_domain(q, p.scal, p.L)) {
+#pragma unroll
+        for (int f = 0; f < F; ++f) e.v[f] = __builtin_nanf("");
+        sn_hg_store<F>(out, e);
+        if (irow) {
+            *reinterpret_cast<int4*>(irow) = make_int4(0, 0, 0, 0);
+            *reinterpret_cast<int4*>(irow + 4) = make_int4(0, 0, 0, 0);
+        }
+        return;
+    }
+    uint32_t row[8];
+    float o[3];
+    G::cell(q, p.scal[l], l, p.log2_T, row, o);
+    SnHgRow<F> c[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) c[k] = sn_hg_load<F>(p.table + row[k] * (uint32_t)F);
+    G::template blend<F>(c, o, e);
     sn_hg_store<F>(out, e);
     if (irow) {
         *reinterpret_cast<int4*>(irow) = make_int4((int)row[0], (int)row[1], (int)row[2], (int)row[3]);
@@ -167,7 +182,7 @@ __global__ __launch_bounds__(SN_HG_BLOCK) void sn_hashgrid_forward_kernel(SnHash
 }
 
 // grad_table[row_k] += fl32(wx wy wz g_f): every lane of the block reaches every shuffle (no early return).
-template <int F, bool MERGE>
+template <int F, bool MERGE, class G = SnHgTorchGrid>
 __global__ __launch_bounds__(SN_HG_BLOCK) void sn_hashgrid_backward_table_kernel(SnHashgridParams p) {
     const int64_t n = (int64_t)blockIdx.x * SN_HG_BLOCK + threadIdx.x;
     const int l = (int)blockIdx.y;
@@ -177,14 +192,14 @@ __global__ __launch_bounds__(SN_HG_BLOCK) void sn_hashgrid_backward_table_kernel
         q[0] = p.q[n * 3];
         q[1] = p.q[n * 3 + 1];
         q[2] = p.q[n * 3 + 2];
-        valid = sn_hg_in_domain(q, p.scal, p.L);
+        valid = G::in_domain(q, p.scal, p.L);
     }
     const float s = p.scal[l];
     uint32_t row[8] = {};
     float o[3] = {0.0f, 0.0f, 0.0f};
     SnHgRow<F> g{};
     if (valid) {
-        sn_hg_cell(q, s, l, p.log2_T, row, o);
+        G::cell(q, s, l, p.log2_T, row, o);
         g = sn_hg_load<F>(p.grad_enc + (n * p.L + l) * F);
     }
     const double ox = o[0], oy = o[1], oz = o[2];
@@ -192,7 +207,7 @@ __global__ __launch_bounds__(SN_HG_BLOCK) void sn_hashgrid_backward_table_kernel
     const int lane = (int)(threadIdx.x & 63u);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const double w = (((SN_HG_XF >> k) & 1u) ? 1.0 - ox : ox) * (((SN_HG_YF >> k) & 1u) ? 1.0 - oy : oy) * (((SN_HG_ZF >> k) & 1u) ? 1.0 - oz : oz);
+        const double w = (((G::XF >> k) & 1u) ? 1.0 - ox : ox) * (((G::YF >> k) & 1u) ? 1.0 - oy : oy) * (((G::ZF >> k) & 1u) ? 1.0 - oz : oz);
         float v[F];
 #pragma unroll
         for (int f = 0; f < F; ++f) v[f] = (float)(w * (double)g.v[f]);
@@ -226,13 +241,13 @@ __global__ __launch_bounds__(SN_HG_BLOCK) void sn_hashgrid_backward_table_kernel
 }
 
 // grad_q_a = sum_l s_l sum_f g_f d enc_f / d o_a, the literal derivative of the blend
-template <int F>
+template <int F, class G = SnHgTorchGrid>
 __global__ __launch_bounds__(SN_HG_BLOCK) void sn_hashgrid_backward_input_kernel(SnHashgridParams p) {
     const int64_t n = (int64_t)blockIdx.x * SN_HG_BLOCK + threadIdx.x;
     if (n >= p.N) return;
     const float q[3] = {p.q[n * 3], p.q[n * 3 + 1], p.q[n * 3 + 2]};
     float* out = p.grad_q + n * 3;
-    if (!sn_hg_in_domain(q, p.scal, p.L)) {
+    if (!G::in_domain(q, p.scal, p.L)) {
         out[0] = out[1] = out[2] = __builtin_nanf("");
         return;
     }
@@ -241,7 +256,7 @@ __global__ __launch_bounds__(SN_HG_BLOCK) void sn_hashgrid_backward_input_kernel
         const float s = p.scal[l];
         uint32_t row[8];
         float o[3];
-        sn_hg_cell(q, s, l, p.log2_T, row, o);
+        G::cell(q, s, l, p.log2_T, row, o);
         SnHgRow<F> c[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) c[k] = sn_hg_load<F>(p.table + row[k] * (uint32_t)F);
@@ -250,7 +265,8 @@ __global__ __launch_bounds__(SN_HG_BLOCK) void sn_hashgrid_backward_input_kernel
         double dx = 0.0, dy = 0.0, dz = 0.0;
 #pragma unroll
         for (int f = 0; f < F; ++f) {
-            const double f0 = c[0].v[f], f1 = c[1].v[f], f2 = c[2].v[f], f3 = c[3].v[f], f4 = c[4].v[f], f5 = c[5].v[f], f6 = c[6].v[f], f7 = c[7].v[f];
+            const double f0 = c[G::slot(0)].v[f], f1 = c[G::slot(1)].v[f], f2 = c[G::slot(2)].v[f], f3 = c[G::slot(3)].v[f], f4 = c[G::slot(4)].v[f],
+                         f5 = c[G::slot(5)].v[f], f6 = c[G::slot(6)].v[f], f7 = c[G::slot(7)].v[f];
             const double f03 = f0 * ox + f3 * rx, f12 = f1 * ox + f2 * rx, f56 = f5 * ox + f6 * rx, f47 = f4 * ox + f7 * rx;
             const double f0312 = f03 * oy + f12 * ry, f4756 = f47 * oy + f56 * ry;
             const double gf = g.v[f];

@@ -12,6 +12,11 @@ non-contiguous tensor is made contiguous.  What gets a gradient: the table, and 
 with fp32 atomics, so two backward passes may differ in its last bits; the features and ``grad_q`` are bit-reproducible.  A point with a
 non-finite coordinate, or with ``|q * scaling| >= 2**30`` at any level, gives NaN features and a NaN ``grad_q`` row and adds nothing to
 the table's gradient.
+
+``grid="tcnn"`` on the three functions below runs the same kernels on tiny-cuda-nn's grid (signerf_amd/include/signerf_hip_hashgrid_tcnn.h; DESIGN.md §4
+"Trainable tcnn grid"): the uniform table ``tcnn_import`` produces, the library's scales, floor / floor + 1 corners in bit order (bit a
+of corner k adds 1 on axis a) and densely indexed coarse levels.  There a point is in domain iff ``fma(scaling, q, 0.5)`` is finite and
+in ``[0, 2**30)`` on every axis at every level; outside it the behaviour is the one described above.
 """
 
 from __future__ import annotations
@@ -25,6 +30,28 @@ from . import _lib
 FEATURES = (1, 2, 4, 8)
 MAX_LEVELS, MAX_LOG2_T = 32, 24
 TAKES = "the hash-grid kernels take fp32 points and fp32 tables"
+GRIDS = {"torch": "sn_hashgrid", "tcnn": "sn_hashgrid_tcnn"}   # grid -> the prefix of its forward / backward entry points
+
+
+def _entry(grid: str, which: str):
+    """(the entry point, its name) of a grid's forward or backward."""
+    if grid not in GRIDS:
+        raise ValueError(f"grid={grid!r}: one of {sorted(GRIDS)} expected")
+    name = f"{GRIDS[grid]}_{which}"
+    return getattr(_lib.load(), name), name
+
+
+def tcnn_levels(scalings, log2_hashmap_size: int):
+    """(res, rows, dense) per level of a tiny-cuda-nn grid as the kernels derive them from its scalings (host only, no device):
+    r = ceil(s) + 1, n = min(next_multiple(r**3, 8), T), dense iff r**3 <= n."""
+    import ctypes as C
+
+    s = [float(v) for v in scalings]
+    L = len(s)
+    arr = (C.c_float * max(L, 1))(*s)
+    res, rows, dense = ((C.c_int32 * max(L, 1))() for _ in range(3))
+    _lib.check(_lib.load().sn_hashgrid_tcnn_levels(arr, L, log2_hashmap_size, res, rows, dense), None, "sn_hashgrid_tcnn_levels")
+    return list(res[:L]), list(rows[:L]), [bool(d) for d in dense[:L]]
 
 
 def _prep(x, name: str) -> Tensor:
@@ -33,18 +60,18 @@ def _prep(x, name: str) -> Tensor:
 
 
 class _HashEncode(torch.autograd.Function):
-    """(q [N,3], table [L*T,F], scalings [L], log2_T) -> enc [N, L*F]."""
+    """(q [N,3], table [L*T,F], scalings [L], log2_T, grid) -> enc [N, L*F]."""
 
     @staticmethod
-    def forward(ctx, q, table, scalings, log2_T):
+    def forward(ctx, q, table, scalings, log2_T, grid="torch"):
         N, L, F = q.shape[0], scalings.shape[0], table.shape[1]
         ctx.save_for_backward(q, table, scalings)   # the backward pass recomputes indices and weights from q
-        ctx.log2_T = log2_T
+        ctx.log2_T, ctx.grid = log2_T, grid
         with torch.cuda.device(q.device):
             enc = torch.empty((N, L * F), dtype=torch.float32, device=q.device)
             if N > 0:
-                _lib.check(_lib.load().sn_hashgrid_forward(_lib.ptr(q), _lib.ptr(table), _lib.ptr(scalings), N, L, log2_T, F, _lib.ptr(enc), None,
-                                                           _lib.current_stream()), None, "sn_hashgrid_forward")
+                fn, name = _entry(grid, "forward")
+                _lib.check(fn(_lib.ptr(q), _lib.ptr(table), _lib.ptr(scalings), N, L, log2_T, F, _lib.ptr(enc), None, _lib.current_stream()), None, name)
         return enc
 
     @staticmethod
@@ -54,18 +81,21 @@ class _HashEncode(torch.autograd.Function):
         N, L, F = q.shape[0], scalings.shape[0], table.shape[1]
         want_q, want_table = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (want_q or want_table):
-            return None, None, None, None
+            return None, None, None, None, None
         g = _prep(g.to(torch.float32), "grad_enc")
         with torch.cuda.device(q.device):
             g_table = torch.zeros_like(table) if want_table else None     # accumulated into by ONE backward call
             g_q = torch.empty_like(q) if want_q else None
             if N > 0:
-                _lib.check(_lib.load().sn_hashgrid_backward(_lib.ptr(q), _lib.ptr(table), _lib.ptr(scalings), _lib.ptr(g), N, L, ctx.log2_T, F,
-                                                            _lib.ptr(g_table), _lib.ptr(g_q), _lib.current_stream()), None, "sn_hashgrid_backward")
-        return g_q, g_table, None, None
+                fn, name = _entry(ctx.grid, "backward")
+                _lib.check(fn(_lib.ptr(q), _lib.ptr(table), _lib.ptr(scalings), _lib.ptr(g), N, L, ctx.log2_T, F, _lib.ptr(g_table), _lib.ptr(g_q),
+                              _lib.current_stream()), None, name)
+        return g_q, g_table, None, None, None
 
 
-def _check(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int):
+def _check(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int, grid: str = "torch"):
+    if grid not in GRIDS:
+        raise ValueError(f"hash_encode: grid={grid!r}: one of {sorted(GRIDS)} expected")
     for x, name in ((q, "q"), (hash_table, "hash_table"), (scalings, "scalings")):   # every dtype before any device
         _lib.typed(x, name, TAKES)
     q, hash_table, scalings = _prep(q, "q"), _prep(hash_table, "hash_table"), _prep(scalings, "scalings").detach()
@@ -86,19 +116,20 @@ def _check(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: i
     return q, hash_table, scalings
 
 
-def hash_encode(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int) -> Tensor:
+def hash_encode(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int, grid: str = "torch") -> Tensor:
     """nerfstudio's ``HashEncoding.pytorch_fwd``: q [..., 3] (the field's positions in [0, 1]), hash_table [L * 2**log2_hashmap_size, F],
-    scalings [L] -> [..., L * F], level-major.  Differentiable once, in ``hash_table`` and (when it requires a gradient) in ``q``."""
-    q, hash_table, scalings = _check(q, hash_table, scalings, log2_hashmap_size)
+    scalings [L] -> [..., L * F], level-major.  Differentiable once, in ``hash_table`` and (when it requires a gradient) in ``q``.
+    ``grid="tcnn"``: tiny-cuda-nn's grid on the same uniform table (the module docstring)."""
+    q, hash_table, scalings = _check(q, hash_table, scalings, log2_hashmap_size, grid)
     lead = q.shape[:-1]
-    enc = _HashEncode.apply(q.reshape(-1, 3), hash_table, scalings, log2_hashmap_size)
+    enc = _HashEncode.apply(q.reshape(-1, 3), hash_table, scalings, log2_hashmap_size, grid)
     return enc.reshape(*lead, enc.shape[-1])
 
 
-def hash_corner_indices(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int):
+def hash_corner_indices(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int, grid: str = "torch"):
     """For inspection and tests, no gradient: (enc [..., L * F], idx [..., L, 8] int32), the table row (with its level's offset) of every
-    corner in nerfstudio's order hashed_0..7."""
-    q, hash_table, scalings = _check(q, hash_table, scalings, log2_hashmap_size)
+    corner in nerfstudio's order hashed_0..7 -- with ``grid="tcnn"`` in that grid's bit order."""
+    q, hash_table, scalings = _check(q, hash_table, scalings, log2_hashmap_size, grid)
     q, hash_table = q.detach(), hash_table.detach()
     lead, L, F = q.shape[:-1], scalings.numel(), hash_table.shape[1]
     N = q.numel() // 3
@@ -106,16 +137,17 @@ def hash_corner_indices(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_ha
         enc = torch.empty((*lead, L * F), dtype=torch.float32, device=q.device)
         idx = torch.empty((*lead, L, 8), dtype=torch.int32, device=q.device)
         if N > 0:
-            _lib.check(_lib.load().sn_hashgrid_forward(_lib.ptr(q), _lib.ptr(hash_table), _lib.ptr(scalings), N, L, log2_hashmap_size, F,
-                                                       _lib.ptr(enc), _lib.ptr(idx), _lib.current_stream()), None, "sn_hashgrid_forward")
+            fn, name = _entry(grid, "forward")
+            _lib.check(fn(_lib.ptr(q), _lib.ptr(hash_table), _lib.ptr(scalings), N, L, log2_hashmap_size, F, _lib.ptr(enc), _lib.ptr(idx),
+                          _lib.current_stream()), None, name)
     return enc, idx
 
 
 def hash_encode_backward(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int, grad_enc: Tensor,
-                         grad_table: Tensor = None, want_grad_q: bool = False):
+                         grad_table: Tensor = None, want_grad_q: bool = False, grid: str = "torch"):
     """The backward entry point as it is, for tests and measurements: ``grad_table`` (or None) is ACCUMULATED INTO, ``grad_q`` (or None)
     is returned.  -> (grad_table, grad_q)."""
-    q, hash_table, scalings = _check(q, hash_table, scalings, log2_hashmap_size)
+    q, hash_table, scalings = _check(q, hash_table, scalings, log2_hashmap_size, grid)
     q, hash_table, grad_enc = q.detach(), hash_table.detach(), _prep(grad_enc, "grad_enc").detach()
     L, F = scalings.numel(), hash_table.shape[1]
     N = q.numel() // 3
@@ -128,7 +160,7 @@ def hash_encode_backward(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_h
     with torch.cuda.device(q.device):
         grad_q = torch.empty_like(q) if want_grad_q else None
         if N > 0:
-            _lib.check(_lib.load().sn_hashgrid_backward(_lib.ptr(q), _lib.ptr(hash_table), _lib.ptr(scalings), _lib.ptr(grad_enc), N, L,
-                                                        log2_hashmap_size, F, _lib.ptr(grad_table), _lib.ptr(grad_q), _lib.current_stream()),
-                       None, "sn_hashgrid_backward")
+            fn, name = _entry(grid, "backward")
+            _lib.check(fn(_lib.ptr(q), _lib.ptr(hash_table), _lib.ptr(scalings), _lib.ptr(grad_enc), N, L, log2_hashmap_size, F,
+                          _lib.ptr(grad_table), _lib.ptr(grad_q), _lib.current_stream()), None, name)
     return grad_table, grad_q

@@ -35,13 +35,20 @@ from .config import NerfactoModelConfig, SIGNeRFModelConfig
 from .engine import BACKGROUNDS, INITIAL_SAMPLERS, PRECISIONS, Engine, wants_half_grid
 
 TRAINING_MLPS = ("torch", "hip")   # config.training_mlp
+_TCNN_NORMALS = ('training_normals with implementation="tcnn": the analytic-normals kernel reads the torch-path grid and the pred-normals '
+                 "stack sits behind tiny-cuda-nn's Frequency encoding; neither is built for training (config.training_tcnn trains the "
+                 "fields without their normals outputs)")
 
 
 # ------------------------------------------------------------------------------------------------------
 # parameter containers (state-dict layout of nerfstudio's "torch" implementation)
 # ------------------------------------------------------------------------------------------------------
 class HashEncoding(nn.Module):
-    """Parameters of nerfstudio's HashEncoding (torch path): ``hash_table`` [L*T, F]."""
+    """Parameters of nerfstudio's HashEncoding (torch path): ``hash_table`` [L*T, F].  ``trainable_tcnn``: a plain attribute
+    the owning model sets under ``config.training_tcnn``; with it the forward of an ``implementation="tcnn"`` grid runs the differentiable
+    tiny-cuda-nn grid (``hashgrid.hash_encode(grid="tcnn")``) instead of raising."""
+
+    trainable_tcnn = False   # (class-level, like MLP.implementation: a module pickled whole before the attribute existed keeps refusing)
 
     def __init__(self, num_levels: int, min_res: int, max_res: int, log2_hashmap_size: int, features_per_level: int = 2,
                  hash_init_scale: float = 0.001, implementation: str = "torch"):
@@ -74,14 +81,18 @@ class HashEncoding(nn.Module):
 
     def forward(self, in_tensor: Tensor) -> Tensor:
         """nerfstudio's ``HashEncoding.forward`` (torch path): positions [..., 3] in [0, 1] -> [..., L * F], differentiable in
-        ``hash_table`` (and in the positions when they require a gradient) through the HIP kernels of ``signerf_amd.hashgrid``."""
-        if self.implementation != "torch":
+        ``hash_table`` (and in the positions when they require a gradient) through the HIP kernels of ``signerf_amd.hashgrid``.  A
+        tiny-cuda-nn grid (positions in [0, 1)) runs that module's ``grid="tcnn"`` form, when the model was built with
+        ``config.training_tcnn``."""
+        if self.implementation != "torch" and not self.trainable_tcnn:
             raise NotImplementedError(f'HashEncoding.forward: implementation={self.implementation!r}: only the torch-path grid is trainable '
-                                      "here; the tiny-cuda-nn grid (its own resolutions, dense coarse levels) has no differentiable kernel")
+                                      "here; the tiny-cuda-nn grid (its own resolutions, dense coarse levels) trains behind "
+                                      "config.training_tcnn=True")
         from . import hashgrid
 
         dev = in_tensor.device if isinstance(in_tensor, Tensor) else None
-        return hashgrid.hash_encode(in_tensor, self.hash_table, self._scalings_on(dev), self.log2_hashmap_size)
+        return hashgrid.hash_encode(in_tensor, self.hash_table, self._scalings_on(dev), self.log2_hashmap_size,
+                                    grid="torch" if self.implementation == "torch" else "tcnn")
 
     def _scalings_on(self, dev) -> Tensor:
         """The scalings are a function of the constructor's arguments: cached per device, NOT a buffer (the state dict stays hash_table only)."""
@@ -280,10 +291,13 @@ _SH4 = (0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.946174695
         0.5900435899266435, 2.890611442640554, 0.4570457994644658, 0.3731763325901154, 1.445305721320277)
 
 
-def _sh4_encoding(directions: Tensor) -> Tensor:
-    """The 16 real SH components of degree < 4 in the eval kernel's convention for the torch path: evaluated on
-    ``get_normalized_directions`` = (d + 1) / 2 (``oracle.nerfacto.direction_encoding``).  [..., 3] -> [..., 16]."""
+def _sh4_encoding(directions: Tensor, remap: str = "torch") -> Tensor:
+    """The 16 real SH components of degree < 4 in the eval kernel's conventions: for the torch path evaluated on
+    ``get_normalized_directions`` = (d + 1) / 2, for ``remap="tcnn"`` on that value mapped back to [-1, 1], as
+    tiny-cuda-nn does (``oracle.nerfacto.direction_encoding``).  [..., 3] -> [..., 16]."""
     d = (directions + 1.0) / 2.0
+    if remap != "torch":
+        d = d * 2.0 - 1.0
     x, y, z = d[..., 0], d[..., 1], d[..., 2]
     xx, yy, zz = x * x, y * y, z * z
     c0, c1, c2, c3, c4, c5, c6, c7, c8, c9, c10 = _SH4
@@ -297,9 +311,9 @@ def _training_q(owner, ray_samples):
     Samples of ``signerf_amd.samplers`` carry both (the sampler kernels' ``q`` / ``selector``, the contraction case); with
     ``disable_scene_contraction`` -- or samples from elsewhere -- they are torch ops on the frustums' positions."""
     cfg = owner.config
-    if cfg.implementation != "torch":
+    if cfg.implementation != "torch" and not cfg.training_tcnn:
         raise NotImplementedError(f"training forward: implementation={cfg.implementation!r}: only the torch-path fields train here (the "
-                                  "tiny-cuda-nn grid has no differentiable kernel)")
+                                  "tiny-cuda-nn grid trains behind config.training_tcnn=True)")
     if cfg.hidden_dim != 64 or cfg.hidden_dim_color != 64:
         raise NotImplementedError("training forward: wide fields (hidden_dim=128) are not built for training")
     q, sel = getattr(ray_samples, "q", None), getattr(ray_samples, "selector", None)
@@ -359,6 +373,8 @@ class NerfactoField(_HipField):
             raise NotImplementedError("forward_training: per-sample normals (analytic or predicted) are built for training behind "
                                       "config.training_normals=True; without it a predict_normals=True model trains without its normals "
                                       "outputs")
+        if compute_normals and cfg.implementation != "torch":
+            raise NotImplementedError(_TCNN_NORMALS)
         if appearance not in ("per_camera", "mean"):
             raise ValueError(f'appearance={appearance!r}: "per_camera" or "mean" expected')
         q, sel = _training_q(owner, ray_samples)
@@ -366,7 +382,7 @@ class NerfactoField(_HipField):
         h = self.mlp_base(q.reshape(-1, 3))
         density = (cfg.average_init_density * _TruncExp.apply(h[:, :1])).reshape(*lead, 1) * sel
         geo = h[:, 1:1 + self.geo_feat_dim]
-        parts = [_sh4_encoding(ray_samples.frustums.directions.reshape(-1, 3)), geo]
+        parts = [_sh4_encoding(ray_samples.frustums.directions.reshape(-1, 3), "torch" if cfg.implementation == "torch" else "tcnn"), geo]
         if cfg.appearance_embed_dim > 0:
             if appearance == "per_camera":
                 if ray_samples.camera_indices is None:
@@ -571,10 +587,16 @@ class NerfactoModel(nn.Module):
         if cfg.training_mlp_precision != "fp32" and cfg.training_mlp != "hip":
             raise NotImplementedError(f'training_mlp_precision={cfg.training_mlp_precision!r} with training_mlp={cfg.training_mlp!r}: the '
                                       'mixed-precision arithmetic is the fused HIP MLP\'s; it needs training_mlp="hip" (the torch stacks are fp32)')
+        if cfg.implementation != "torch" and cfg.training_tcnn:
+            if cfg.training_normals:
+                raise NotImplementedError(_TCNN_NORMALS)
+            for m in self.modules():
+                if isinstance(m, HashEncoding):
+                    m.trainable_tcnn = True
         if cfg.training_mlp == "hip":
-            if cfg.implementation != "torch":
+            if cfg.implementation != "torch" and not cfg.training_tcnn:
                 raise NotImplementedError(f'training_mlp="hip" with implementation={cfg.implementation!r}: the HIP MLP reads the nn.Linear '
-                                          "weights of the torch-path fields; a tiny-cuda-nn field has no trainable forward here")
+                                          "weights of the torch-path fields; a tiny-cuda-nn field trains behind config.training_tcnn=True")
             stacks = [self.field.mlp_base.mlp, self.field.mlp_head] + [net.mlp_base.mlp for net in self.proposal_networks]
             if cfg.predict_normals:
                 stacks.append(self.field.mlp_pred_normals)

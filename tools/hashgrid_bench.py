@@ -16,6 +16,11 @@ Per shape, forward + backward (table gradient, zeroing it included), the median 
 and beside them what the bytes the table gradient adds would cost at the guide's two float-atomic rates (scattered rows, contiguous).
 
     python tools/hashgrid_bench.py [--reps 50] [--out profiles/hashgrid_bench.json]
+
+``--grid tcnn`` measures the trainable tiny-cuda-nn grid (hashgrid.hash_encode(grid="tcnn"), csrc/sn_hashgrid_tcnn.h; DESIGN.md §4
+"Trainable tcnn grid") on the same shapes and points, with the library's own scales and its dense coarse levels, and writes
+profiles/hashgrid_tcnn_bench.json.  Its reference, in the same process, is the torch-path grid's kernels at their shipped threshold
+(``torch_grid_shipped``) instead of the torch ops; each record names the dense levels.
 """
 import argparse
 import json
@@ -28,6 +33,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from oracle import nerfacto as onf  # noqa: E402
+from oracle import tcnn_layout  # noqa: E402
 from signerf_amd import _lib, hashgrid  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -35,8 +41,10 @@ ap.add_argument("--rays", type=int, default=4096)
 ap.add_argument("--reps", type=int, default=50)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--no-sweep", action="store_true")
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hashgrid_bench.json"))
+ap.add_argument("--grid", choices=("torch", "tcnn"), default="torch")
+ap.add_argument("--out", default=None)
 a = ap.parse_args()
+a.out = a.out or os.path.join(ROOT, "profiles", "hashgrid_bench.json" if a.grid == "torch" else "hashgrid_tcnn_bench.json")
 dev = torch.device("cuda", 0)
 ENV = "SN_HASHGRID_MERGE_MAX_SCALE"
 SHAPES = {"main": dict(samples=48, L=16, log2_T=19, base=16, max_res=2048), "proposal_0": dict(samples=256, L=5, log2_T=17, base=16, max_res=128),
@@ -82,18 +90,24 @@ results = {}
 for name, sh in SHAPES.items():
     L, log2_T = sh["L"], sh["log2_T"]
     q = ray_points(a.rays, sh["samples"], seed=len(name)).to(dev)
-    s = onf.hash_scalings(L, sh["base"], sh["max_res"])
-    s_dev = s.to(dev)
+    s_torch = onf.hash_scalings(L, sh["base"], sh["max_res"])
+    meta = tcnn_layout.grid_meta(L, sh["base"], sh["max_res"], log2_T) if a.grid == "tcnn" else None
+    s = s_torch if meta is None else torch.tensor(meta.scales, dtype=torch.float32)
+    s_dev, s_torch_dev = s.to(dev), s_torch.to(dev)
     table = ((torch.rand((L << log2_T, 2), generator=torch.Generator().manual_seed(1)) * 2 - 1) * 1e-3).to(dev).requires_grad_()
     g = torch.randn(q.shape[0], L * 2, generator=torch.Generator().manual_seed(2)).to(dev)
 
     def hip_forward():
         with torch.no_grad():
-            hashgrid.hash_encode(q, table, s_dev, log2_T)
+            hashgrid.hash_encode(q, table, s_dev, log2_T, grid=a.grid)
 
     def hip_step():
         table.grad = None
-        hashgrid.hash_encode(q, table, s_dev, log2_T).backward(g)
+        hashgrid.hash_encode(q, table, s_dev, log2_T, grid=a.grid).backward(g)
+
+    def torch_grid_step():
+        table.grad = None
+        hashgrid.hash_encode(q, table, s_torch_dev, log2_T).backward(g)
 
     def torch_step():
         table.grad = None
@@ -102,6 +116,9 @@ for name, sh in SHAPES.items():
     added = q.shape[0] * L * 8 * 2 * 4
     rec = {"points": q.shape[0], "levels": L, "log2_T": log2_T, "scalings": s.tolist(), "grad_table_bytes_added": added,
            "atomic_rate_ms": {"scattered_0.08_TBps": round(added / (SCATTERED_TBPS * 1e9), 3), "contiguous_1.3_TBps": round(added / (CONTIGUOUS_TBPS * 1e9), 3)}}
+    if meta is not None:
+        rec["dense_levels"] = [l for l in range(L) if meta.dense[l]]
+        rec["level_rows"] = [meta.offsets[l + 1] - meta.offsets[l] for l in range(L)]
     rec["hip_forward"] = span(hip_forward)
     set_merge(-1.0)
     rec["hip_a"] = span(hip_step)
@@ -112,16 +129,21 @@ for name, sh in SHAPES.items():
             rec["hip_merge_upto"].append(dict(level=k, max_scale=s[k].item(), **span(hip_step)))
     set_merge(None)
     rec["hip_shipped"] = span(hip_step)
-    rec["torch"] = span(torch_step)
-    rec["torch_over_hip_shipped"] = round(rec["torch"]["ms_median"] / rec["hip_shipped"]["ms_median"], 2)
+    if a.grid == "tcnn":
+        rec["torch_grid_shipped"] = span(torch_grid_step)
+        rec["tcnn_over_torch_grid"] = round(rec["hip_shipped"]["ms_median"] / rec["torch_grid_shipped"]["ms_median"], 2)
+    else:
+        rec["torch"] = span(torch_step)
+        rec["torch_over_hip_shipped"] = round(rec["torch"]["ms_median"] / rec["hip_shipped"]["ms_median"], 2)
     results[name] = rec
     print(name, json.dumps(rec), flush=True)
     del table, q, g
     torch.cuda.empty_cache()
 
-doc = {"tool": "tools/hashgrid_bench.py", "device": torch.cuda.get_device_name(0), "rays": a.rays, "reps": a.reps,
+doc = {"tool": "tools/hashgrid_bench.py", "grid": a.grid, "device": torch.cuda.get_device_name(0), "rays": a.rays, "reps": a.reps,
        "note": "forward + backward (table gradient) per call, ms, median of hipEvent spans; `torch`: oracle.nerfacto.hash_encode as fp32 torch "
-               "ops with autograd on the same GPU in the same process; points are ray-ordered samples through the contracted scene",
+               "ops with autograd on the same GPU in the same process; `torch_grid_shipped` (--grid tcnn): the torch-path grid's kernels "
+               "on the same points, table and process; points are ray-ordered samples through the contracted scene",
        "results": results}
 os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
 with open(a.out, "w") as f:
