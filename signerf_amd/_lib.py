@@ -370,6 +370,16 @@ _add("hashgrid_tcnn", version=1, recorded=False, extension=True, functions={
     "sn_hashgrid_tcnn_backward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p]),
 })
 
+# signerf_amd/include/signerf_hip_hashgrid_ordered.h: the ordered table gradient of both grids (its host test: tests/test_hashgrid_ordered_host.py)
+_add("hashgrid_ordered", version=1, recorded=False, extension=True, functions={
+    "sn_hashgrid_ordered_abi_version": (C.c_int, []),
+    "sn_hashgrid_ordered_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "sn_hashgrid_ordered_backward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p, C.c_size_t,
+                                               C.c_void_p]),
+    "sn_hashgrid_ordered_tcnn_backward": (C.c_int, [_FP, _FP, _FP, _FP, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _FP, _FP, C.c_void_p, C.c_size_t,
+                                                    C.c_void_p]),
+})
+
 
 class SnSamplerRays(_Sized):
     _fields_ = [

@@ -132,6 +132,12 @@ class NerfactoModelConfig(InstantiateConfig):
     folded from the library's input padding) are ordinary parameters and train, so the result is saved in this package's state-dict
     layout, not as tiny-cuda-nn's flat vectors.  ``training_normals`` with it raises ``NotImplementedError``.  Off by default: a tcnn model
     then refuses every training entry point, as before.  Ignored by ``implementation="torch"``."""
+    training_hashgrid_grad: str = "atomic"
+    """How the hash grids' table gradient is summed in the training forward's backward pass (``HashEncoding.table_grad`` of the main field
+    and of every proposal network): "atomic" -- fp32 atomic adds, whose arrival order differs from run to run, as before -- or "ordered":
+    every contribution stored, sorted by row and summed in fp64 in a fixed order (``hashgrid.hash_encode(table_grad="ordered")``; DESIGN.md
+    §4 "Ordered table gradient"), so that two runs from one seed give the same bits.  Works with ``implementation="torch"`` and, under
+    ``training_tcnn``, with "tcnn".  The features and the eval render do not depend on it."""
     dense_levels: int = 0
     """Memory budget of the derived gather buffers the HIP library builds beside the uploaded tables (``SnFieldDesc.dense_levels``):
     0 = default (the 11 coarsest levels of the main grid get a de-hashed copy: 1.26 GB per model for nerfacto's grid, + 0.47 GB of x-paired

@@ -10,6 +10,7 @@
 #include "../../include/signerf_hip_losses.h"
 #include "../../include/signerf_hip_hashgrid.h"
 #include "../include/signerf_hip_hashgrid_tcnn.h"
+#include "../include/signerf_hip_hashgrid_ordered.h"
 #include "../../include/signerf_hip_sampler.h"
 #include "../../include/signerf_hip_mlp.h"
 #include "../../include/signerf_hip_train_normals.h"
@@ -47,6 +48,7 @@
 #include "sn_losses.h"
 #include "sn_hashgrid.h"
 #include "sn_hashgrid_tcnn.h"
+#include "sn_hashgrid_ordered.h"
 #include "sn_sampler.h"
 #include "sn_mlp.h"
 #include "sn_mlp_half.h"
@@ -1426,6 +1428,7 @@ int sn_field_forward_geo(SnHandle h, int32_t which, const float* positions, cons
 #include "sn_api_losses.h"
 #include "sn_api_hashgrid.h"
 #include "sn_api_hashgrid_tcnn.h"
+#include "sn_api_hashgrid_ordered.h"
 #include "sn_api_sampler.h"
 #include "sn_api_mlp.h"
 #include "sn_api_train_normals.h"

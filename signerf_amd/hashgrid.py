@@ -8,8 +8,11 @@ ops (DESIGN.md §4 "Trainable hash grid").
 
 Inputs are fp32 GPU tensors: another dtype raises ``TypeError``, a CPU tensor raises ``SignerfHipError`` (there is no CPU path), a
 non-contiguous tensor is made contiguous.  What gets a gradient: the table, and ``q`` when it requires one; never the scalings.  The op is
-``once_differentiable``: a second-order request (analytic-normal losses) raises instead of being silently wrong.  ``grad_table`` is summed
-with fp32 atomics, so two backward passes may differ in its last bits; the features and ``grad_q`` are bit-reproducible.  A point with a
+``once_differentiable``: a second-order request (analytic-normal losses) raises instead of being silently wrong.  With the default
+``table_grad="atomic"`` ``grad_table`` is summed with fp32 atomics, so two backward passes may differ in its last bits; with
+``table_grad="ordered"`` (signerf_amd/include/signerf_hip_hashgrid_ordered.h; DESIGN.md §4 "Ordered table gradient") every contribution is stored,
+sorted by row and summed in fp64 in a fixed order, without a float atomic, and two backward passes give the same bits.  The features and
+``grad_q`` are bit-reproducible either way.  A point with a
 non-finite coordinate, or with ``|q * scaling| >= 2**30`` at any level, gives NaN features and a NaN ``grad_q`` row and adds nothing to
 the table's gradient.
 
@@ -31,6 +34,8 @@ FEATURES = (1, 2, 4, 8)
 MAX_LEVELS, MAX_LOG2_T = 32, 24
 TAKES = "the hash-grid kernels take fp32 points and fp32 tables"
 GRIDS = {"torch": "sn_hashgrid", "tcnn": "sn_hashgrid_tcnn"}   # grid -> the prefix of its forward / backward entry points
+TABLE_GRADS = ("atomic", "ordered")
+ORDERED = {"torch": "sn_hashgrid_ordered_backward", "tcnn": "sn_hashgrid_ordered_tcnn_backward"}
 
 
 def _entry(grid: str, which: str):
@@ -39,6 +44,28 @@ def _entry(grid: str, which: str):
         raise ValueError(f"grid={grid!r}: one of {sorted(GRIDS)} expected")
     name = f"{GRIDS[grid]}_{which}"
     return getattr(_lib.load(), name), name
+
+
+def _check_table_grad(table_grad: str) -> None:
+    if table_grad not in TABLE_GRADS:
+        raise ValueError(f"table_grad={table_grad!r}: one of {TABLE_GRADS} expected")
+
+
+def _backward(grid: str, table_grad: str, q, table, scalings, g, N, L, log2_T, F, g_table, g_q) -> None:
+    """The backward entry point of a grid in the chosen form of the table gradient.  The ordered form's workspace is a uint8 tensor on the
+    current device: torch's allocator keeps it alive for the stream it was allocated on."""
+    if table_grad == "atomic":
+        fn, name = _entry(grid, "backward")
+        _lib.check(fn(_lib.ptr(q), _lib.ptr(table), _lib.ptr(scalings), _lib.ptr(g), N, L, log2_T, F, _lib.ptr(g_table), _lib.ptr(g_q),
+                      _lib.current_stream()), None, name)
+        return
+    if grid not in GRIDS:
+        raise ValueError(f"grid={grid!r}: one of {sorted(GRIDS)} expected")
+    lib, name = _lib.load(), ORDERED[grid]
+    size = lib.sn_hashgrid_ordered_workspace_bytes(N, L, log2_T, F) if g_table is not None else 0   # (0: the entry point says why)
+    ws = torch.empty(size, dtype=torch.uint8, device=q.device) if size else None
+    _lib.check(getattr(lib, name)(_lib.ptr(q), _lib.ptr(table), _lib.ptr(scalings), _lib.ptr(g), N, L, log2_T, F, _lib.ptr(g_table), _lib.ptr(g_q),
+                                  _lib.ptr(ws), size, _lib.current_stream()), None, name)
 
 
 def tcnn_levels(scalings, log2_hashmap_size: int):
@@ -60,13 +87,13 @@ def _prep(x, name: str) -> Tensor:
 
 
 class _HashEncode(torch.autograd.Function):
-    """(q [N,3], table [L*T,F], scalings [L], log2_T, grid) -> enc [N, L*F]."""
+    """(q [N,3], table [L*T,F], scalings [L], log2_T, grid, table_grad) -> enc [N, L*F]."""
 
     @staticmethod
-    def forward(ctx, q, table, scalings, log2_T, grid="torch"):
+    def forward(ctx, q, table, scalings, log2_T, grid="torch", table_grad="atomic"):
         N, L, F = q.shape[0], scalings.shape[0], table.shape[1]
         ctx.save_for_backward(q, table, scalings)   # the backward pass recomputes indices and weights from q
-        ctx.log2_T, ctx.grid = log2_T, grid
+        ctx.log2_T, ctx.grid, ctx.table_grad = log2_T, grid, table_grad
         with torch.cuda.device(q.device):
             enc = torch.empty((N, L * F), dtype=torch.float32, device=q.device)
             if N > 0:
@@ -81,16 +108,14 @@ class _HashEncode(torch.autograd.Function):
         N, L, F = q.shape[0], scalings.shape[0], table.shape[1]
         want_q, want_table = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (want_q or want_table):
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         g = _prep(g.to(torch.float32), "grad_enc")
         with torch.cuda.device(q.device):
             g_table = torch.zeros_like(table) if want_table else None     # accumulated into by ONE backward call
             g_q = torch.empty_like(q) if want_q else None
             if N > 0:
-                fn, name = _entry(ctx.grid, "backward")
-                _lib.check(fn(_lib.ptr(q), _lib.ptr(table), _lib.ptr(scalings), _lib.ptr(g), N, L, ctx.log2_T, F, _lib.ptr(g_table), _lib.ptr(g_q),
-                              _lib.current_stream()), None, name)
-        return g_q, g_table, None, None, None
+                _backward(ctx.grid, ctx.table_grad, q, table, scalings, g, N, L, ctx.log2_T, F, g_table, g_q)
+        return g_q, g_table, None, None, None, None
 
 
 def _check(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int, grid: str = "torch"):
@@ -116,13 +141,16 @@ def _check(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: i
     return q, hash_table, scalings
 
 
-def hash_encode(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int, grid: str = "torch") -> Tensor:
+def hash_encode(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int, grid: str = "torch",
+                table_grad: str = "atomic") -> Tensor:
     """nerfstudio's ``HashEncoding.pytorch_fwd``: q [..., 3] (the field's positions in [0, 1]), hash_table [L * 2**log2_hashmap_size, F],
     scalings [L] -> [..., L * F], level-major.  Differentiable once, in ``hash_table`` and (when it requires a gradient) in ``q``.
-    ``grid="tcnn"``: tiny-cuda-nn's grid on the same uniform table (the module docstring)."""
+    ``grid="tcnn"``: tiny-cuda-nn's grid on the same uniform table (the module docstring).  ``table_grad``: "atomic" (fp32 atomic adds) or
+    "ordered" (the bit-reproducible fp64 sum in a fixed order) for the table's gradient; the features do not depend on it."""
+    _check_table_grad(table_grad)
     q, hash_table, scalings = _check(q, hash_table, scalings, log2_hashmap_size, grid)
     lead = q.shape[:-1]
-    enc = _HashEncode.apply(q.reshape(-1, 3), hash_table, scalings, log2_hashmap_size, grid)
+    enc = _HashEncode.apply(q.reshape(-1, 3), hash_table, scalings, log2_hashmap_size, grid, table_grad)
     return enc.reshape(*lead, enc.shape[-1])
 
 
@@ -144,9 +172,10 @@ def hash_corner_indices(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_ha
 
 
 def hash_encode_backward(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_hashmap_size: int, grad_enc: Tensor,
-                         grad_table: Tensor = None, want_grad_q: bool = False, grid: str = "torch"):
+                         grad_table: Tensor = None, want_grad_q: bool = False, grid: str = "torch", table_grad: str = "atomic"):
     """The backward entry point as it is, for tests and measurements: ``grad_table`` (or None) is ACCUMULATED INTO, ``grad_q`` (or None)
-    is returned.  -> (grad_table, grad_q)."""
+    is returned.  -> (grad_table, grad_q).  ``table_grad="ordered"`` calls the ordered entry point of the grid with a workspace of its own."""
+    _check_table_grad(table_grad)
     q, hash_table, scalings = _check(q, hash_table, scalings, log2_hashmap_size, grid)
     q, hash_table, grad_enc = q.detach(), hash_table.detach(), _prep(grad_enc, "grad_enc").detach()
     L, F = scalings.numel(), hash_table.shape[1]
@@ -160,7 +189,5 @@ def hash_encode_backward(q: Tensor, hash_table: Tensor, scalings: Tensor, log2_h
     with torch.cuda.device(q.device):
         grad_q = torch.empty_like(q) if want_grad_q else None
         if N > 0:
-            fn, name = _entry(grid, "backward")
-            _lib.check(fn(_lib.ptr(q), _lib.ptr(hash_table), _lib.ptr(scalings), _lib.ptr(grad_enc), N, L, log2_hashmap_size, F,
-                          _lib.ptr(grad_table), _lib.ptr(grad_q), _lib.current_stream()), None, name)
+            _backward(grid, table_grad, q, hash_table, scalings, grad_enc, N, L, log2_hashmap_size, F, grad_table, grad_q)
     return grad_table, grad_q

@@ -35,6 +35,7 @@ from .config import NerfactoModelConfig, SIGNeRFModelConfig
 from .engine import BACKGROUNDS, INITIAL_SAMPLERS, PRECISIONS, Engine, wants_half_grid
 
 TRAINING_MLPS = ("torch", "hip")   # config.training_mlp
+TRAINING_HASHGRID_GRADS = ("atomic", "ordered")   # config.training_hashgrid_grad (hashgrid.TABLE_GRADS)
 _TCNN_NORMALS = ('training_normals with implementation="tcnn": the analytic-normals kernel reads the torch-path grid and the pred-normals '
                  "stack sits behind tiny-cuda-nn's Frequency encoding; neither is built for training (config.training_tcnn trains the "
                  "fields without their normals outputs)")
@@ -46,9 +47,11 @@ _TCNN_NORMALS = ('training_normals with implementation="tcnn": the analytic-norm
 class HashEncoding(nn.Module):
     """Parameters of nerfstudio's HashEncoding (torch path): ``hash_table`` [L*T, F].  ``trainable_tcnn``: a plain attribute
     the owning model sets under ``config.training_tcnn``; with it the forward of an ``implementation="tcnn"`` grid runs the differentiable
-    tiny-cuda-nn grid (``hashgrid.hash_encode(grid="tcnn")``) instead of raising."""
+    tiny-cuda-nn grid (``hashgrid.hash_encode(grid="tcnn")``) instead of raising.  ``table_grad``: a plain attribute too, "atomic" or "ordered"
+    (``config.training_hashgrid_grad``): how the backward pass of ``forward`` sums the table's gradient."""
 
     trainable_tcnn = False   # (class-level, like MLP.implementation: a module pickled whole before the attribute existed keeps refusing)
+    table_grad = "atomic"    # (class-level for the same reason; not state)
 
     def __init__(self, num_levels: int, min_res: int, max_res: int, log2_hashmap_size: int, features_per_level: int = 2,
                  hash_init_scale: float = 0.001, implementation: str = "torch"):
@@ -92,7 +95,7 @@ class HashEncoding(nn.Module):
 
         dev = in_tensor.device if isinstance(in_tensor, Tensor) else None
         return hashgrid.hash_encode(in_tensor, self.hash_table, self._scalings_on(dev), self.log2_hashmap_size,
-                                    grid="torch" if self.implementation == "torch" else "tcnn")
+                                    grid="torch" if self.implementation == "torch" else "tcnn", table_grad=self.table_grad)
 
     def _scalings_on(self, dev) -> Tensor:
         """The scalings are a function of the constructor's arguments: cached per device, NOT a buffer (the state dict stays hash_table only)."""
@@ -587,6 +590,11 @@ class NerfactoModel(nn.Module):
         if cfg.training_mlp_precision != "fp32" and cfg.training_mlp != "hip":
             raise NotImplementedError(f'training_mlp_precision={cfg.training_mlp_precision!r} with training_mlp={cfg.training_mlp!r}: the '
                                       'mixed-precision arithmetic is the fused HIP MLP\'s; it needs training_mlp="hip" (the torch stacks are fp32)')
+        if cfg.training_hashgrid_grad not in TRAINING_HASHGRID_GRADS:
+            raise ValueError(f"training_hashgrid_grad={cfg.training_hashgrid_grad!r}: one of {sorted(TRAINING_HASHGRID_GRADS)} expected")
+        if cfg.training_hashgrid_grad != "atomic":
+            for net in [self.field.mlp_base] + [net.mlp_base for net in self.proposal_networks]:
+                net.encoder.table_grad = cfg.training_hashgrid_grad
         if cfg.implementation != "torch" and cfg.training_tcnn:
             if cfg.training_normals:
                 raise NotImplementedError(_TCNN_NORMALS)
